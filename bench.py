@@ -4,6 +4,7 @@
 configs[3] = the same workload sharded over the GPUs of a node).
 
     python bench.py --gpus 1 --steps 2000 --warmup 50
+    python bench.py --gpus 1 --steps 2000 --warmup 50 --dump-outputs bench_outputs   # + bench_outputs/<field>.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \
         --master-port 29500 bench.py --gpus 8 --steps 2000 --warmup 50
 
@@ -165,6 +166,10 @@ def parse_args():
     ap.add_argument("--no-other-contact-models", action="store_true", help="skip the secondary RigidContacts / RelaxedRigidContacts figures")
     ap.add_argument("--no-python-loop", action="store_true", help="skip the secondary `python_step_loop` figure (the rocprofv3 passes of tools/profile_round.sh: "
                     "its 12 000 plain launches would be averaged into the per-dispatch statistics of the step kernel)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the state the timed path left after its last step (rank 0's environments, "
+                    "the fields of JaxSimModelData, [N, ...] in the run's precision) as DIR/<field>.npy; at most 64 MB in all, "
+                    "a fixed seeded sample of the environments beyond that")
     ap.add_argument("--dry-run-bootstrap", action="store_true",
                     help="no GPU work: run only the multi-rank bootstrap of this script (job key, id exchange through the "
                     "rendezvous file, host collective, shard bounds) and print what a rank-0 line would say about it")
@@ -429,6 +434,26 @@ def cpu_baseline(model, block, budget_s):
         f"reference formulation, gcc -O3 -march=native, OpenMP, best of several team sizes = {nt} threads on a "
         f"{cores}-CPU host), {np.dtype(dtype).name}, {dt:.1f} s",
     }
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, model, block):
+    """--dump-outputs: the state block ``[rows, N]`` the timed steps left, as the arrays a caller of ``js.model.step``
+    receives (the fields of JaxSimModelData, ``[N, ...]``), one ``out_dir/<field>.npy`` each.  Larger than
+    DUMP_MAX_BYTES: the environments of a fixed seeded sample (sorted indices), the same from run to run."""
+    from jaxsim_amd import state as st
+
+    n_envs = block.shape[1]
+    keep = min(n_envs, max(1, DUMP_MAX_BYTES // (block.shape[0] * block.itemsize)))
+    envs = np.arange(n_envs) if keep == n_envs else np.sort(np.random.default_rng(0).choice(n_envs, keep, replace=False))
+    fields = st.unpack_state(st.StateLayout.of(model), block[:, envs])
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in fields.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+    return {"dir": out_dir, "arrays": sorted(fields), "envs": int(keep), "of_envs": int(n_envs),
+            "sample": None if keep == n_envs else "numpy default_rng(0).choice(of_envs, envs, replace=False), sorted"}
 
 
 def timed_repetitions(timed_region, run_steps, steps, reps, stream, barrier, lib):
@@ -742,6 +767,8 @@ def main():
     # region of a short request, e.g. --steps 20 = 0.2 ms, is otherwise at the mercy of one host hiccup).
     reps = 5 if args.steps >= 500 else 9
     wall, evs = timed_repetitions(timed_region, run_steps, args.steps, reps, stream, barrier, lib)
+    # (the secondary figures below advance the same state further: its copy is taken here, outside every timed region)
+    dumped = dump_outputs(args.dump_outputs, model, data.state_block()) if args.dump_outputs and rank == 0 else None
     per_rank_ms = None
     if comm is not None:  # max over ranks, repetition by repetition
         gathered = [np.asarray(comm.all_gather_scalars(w), dtype=np.float64) for w in wall]
@@ -1053,6 +1080,7 @@ def main():
                               "controlled_and_recorded_us_per_step": recorded_us,
                               "note": "same steps as one jxs_rollout launch; `controlled`: with one block of joint torques per step "
                                       "(jxs_rollout_controlled); `recorded`: and the state block after every step stored (jxs_rollout_recorded); secondary figures, not `value`"},
+            "dump_outputs": dumped,
         }
         if saturated is not None:
             if "env_steps_per_s" in saturated:

@@ -73,3 +73,26 @@ def test_bench_global_batch_is_strong_scaling_gpu():
     d = run_bench("--gpus", "1", "--global-batch", "2048", *FAST, "--no-cpu-baseline")
     assert d["scaling"] == "strong" and d["config"]["global_batch"] == 2048 and d["config"]["envs_per_gpu"] == 2048
     assert abs(d["value"] - 2048 / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_same_from_run_to_run_gpu(tmp_path):
+    """`--dump-outputs DIR`: the state the timed steps left, as the fields of JaxSimModelData ([1024, ...], float32),
+    and the same arrays from two runs with the same arguments (same seeded inputs, same kernels)."""
+    import numpy as np
+
+    flags = ["--gpus", "1", *FAST, "--no-cpu-baseline", "--no-python-loop"]
+    lines = [run_bench(*flags, "--dump-outputs", str(tmp_path / f"run{i}")) for i in range(2)]
+    names = ["base_angular_velocity", "base_linear_velocity", "base_position", "base_quaternion", "joint_positions",
+             "joint_velocities", "tangential_deformation"]  # fmt: skip
+    for i, d in enumerate(lines):
+        assert d["steps"] == 20 and d["dump_outputs"]["arrays"] == names and d["dump_outputs"]["envs"] == 1024
+        assert sorted(p.stem for p in (tmp_path / f"run{i}").glob("*.npy")) == names
+    shapes = {"base_position": (1024, 3), "base_quaternion": (1024, 4), "joint_positions": (1024, 23), "tangential_deformation": (1024, 32, 3)}
+    for name in names:
+        a, b = (np.load(tmp_path / f"run{i}" / f"{name}.npy") for i in range(2))
+        assert a.dtype == np.float32 and a.shape == shapes.get(name, a.shape) and a.shape[0] == 1024
+        np.testing.assert_array_equal(a, b)
+    q = np.load(tmp_path / "run0" / "base_quaternion.npy")
+    ok = np.isfinite(q).all(axis=1)
+    assert ok.mean() > 0.9 and np.allclose(np.linalg.norm(q[ok], axis=1), 1.0, atol=1e-4)

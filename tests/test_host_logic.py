@@ -498,3 +498,32 @@ def test_fp32_relaxed_contacts_with_a_negligible_regulariser_are_refused(models,
         runtime.fp32_relaxed_defaults_guard(helpers.relaxed_model(models("anymal"), helpers.ANYMAL_FEET_16), np.float32)
     monkeypatch.setenv("JAXSIM_AMD_FP32_RELAXED_UNCHECKED", "1")
     runtime.fp32_relaxed_defaults_guard(box, np.float32)
+
+
+def test_bench_dump_outputs_fields_and_fixed_sample(models, tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the fields of JaxSimModelData cut from the state block, [N, ...] in the block's own
+    precision; past the size limit, whole environments of one fixed sample, the same on every call."""
+    import bench
+
+    model = models("icub")
+    lay = st.StateLayout.of(model)
+    block = np.random.default_rng(5).standard_normal((lay.n_rows, 40)).astype(np.float32)
+    ref = st.unpack_state(lay, block)
+    info = bench.dump_outputs(str(tmp_path / "all"), model, block)
+    assert info["envs"] == info["of_envs"] == 40 and info["sample"] is None
+    assert sorted(p.stem for p in (tmp_path / "all").glob("*.npy")) == info["arrays"] == sorted(ref)
+    for name, a in ref.items():
+        got = np.load(tmp_path / "all" / f"{name}.npy")
+        assert got.dtype == np.float32 and np.array_equal(got, a)
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", lay.n_rows * block.itemsize * 10)
+    info = bench.dump_outputs(str(tmp_path / "s1"), model, block)
+    bench.dump_outputs(str(tmp_path / "s2"), model, block)
+    assert info["envs"] == 10 and info["of_envs"] == 40 and info["sample"]
+    arrays = {name: np.load(tmp_path / "s1" / f"{name}.npy") for name in ref}
+    assert sum(a.nbytes for a in arrays.values()) <= bench.DUMP_MAX_BYTES
+    for name, a in arrays.items():
+        assert np.array_equal(a, np.load(tmp_path / "s2" / f"{name}.npy"))
+    cols = [int(np.flatnonzero((ref["joint_positions"] == row).all(axis=1))[0]) for row in arrays["joint_positions"]]
+    assert cols == sorted(set(cols))
+    for name, a in arrays.items():
+        assert np.array_equal(a, ref[name][cols])
