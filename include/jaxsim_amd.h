@@ -314,6 +314,41 @@ int jxs_mass_matrix(jxs_model* model, const void* state, void* out_M, int N, voi
  * zero (a fixed base does not accelerate).                                                       */
 int jxs_mass_matrix_inverse(jxs_model* model, const void* state, void* out_Minv, int N, void* stream);
 
+/* Centroidal momentum, CoM and energies, one launch (jaxsim.api.com: com_position, com_linear_velocity,
+ * centroidal_momentum, centroidal_momentum_jacobian, locked_centroidal_spatial_inertia, average_centroidal_velocity
+ * (_jacobian), src/jaxsim/api/com.py; jaxsim.api.model: total_momentum(_jacobian), locked_spatial_inertia,
+ * average_velocity(_jacobian), kinetic_energy, potential_energy, mechanical_energy, src/jaxsim/api/model.py:1988-2175,
+ * 2397-2453).  One leaves-to-root sweep of the composite inertia, subtree momentum and subtree kinetic energy
+ * (rbda/crba.py:10-170).  G[W] = (W_p_CoM, world axes); the generalized velocity is the stored one, the base velocity of
+ * a fixed-base model included (like the reference's).
+ *   out_record = [JXS_CENTROIDAL_ROWS][N]:
+ *     rows  0.. 2  JXS_CENTROIDAL_COM        W_p_CoM (as the cached link transforms place the links)
+ *     rows  3.. 8  JXS_CENTROIDAL_MOMENTUM   centroidal momentum h_G in G[W]: linear; angular about the CoM
+ *     rows  9..14  JXS_CENTROIDAL_INERTIA    rotational inertia I_G about the CoM, world axes: xx, xy, xz, yy, yz, zz.
+ *                                            The locked centroidal inertia in G[W] is diag(m 1, I_G) -- for a model
+ *                                            whose base link has a translated pose (suc_H_i[0] = (1, d)) the CoM of
+ *                                            the dynamics sits at W_p_CoM - R_B d: blocks m S(e)^T, I_G + m S(e) S(e)^T
+ *                                            with e = -R_B d, as the reference's congruence gives
+ *     rows 15..20  JXS_CENTROIDAL_AVG_VEL    average centroidal velocity in G[W]: linear (= CoM velocity); angular
+ *     row  21      JXS_CENTROIDAL_KINETIC    kinetic energy 1/2 nu^T M nu
+ *     row  22      JXS_CENTROIDAL_POTENTIAL  potential energy AS THE REFERENCE COMPUTES IT: m z_CoM gravity with
+ *                                            gravity = -9.81, i.e. -m g z (so K - U, not K + U, is conserved)
+ *     row  23      JXS_CENTROIDAL_MASS       total mass
+ *   out_cmm = [6*(6+n)][N] or NULL: the centroidal momentum matrix A_G in G[W] (row r, column c at row index
+ *     r*(6+n)+c), for the generalized velocity in MIXED representation; the other representations are the 6x6
+ *     input / output transforms of api/com.py applied by the caller.
+ * Every entry of both outputs is written by the kernel: no allocation, no memset, no host synchronisation (legal
+ * inside a stream capture).                                                                         */
+#define JXS_CENTROIDAL_COM 0
+#define JXS_CENTROIDAL_MOMENTUM 3
+#define JXS_CENTROIDAL_INERTIA 9
+#define JXS_CENTROIDAL_AVG_VEL 15
+#define JXS_CENTROIDAL_KINETIC 21
+#define JXS_CENTROIDAL_POTENTIAL 22
+#define JXS_CENTROIDAL_MASS 23
+#define JXS_CENTROIDAL_ROWS 24
+int jxs_centroidal(jxs_model* model, const void* state, void* out_record, void* out_cmm, int N, void* stream);
+
 /* jacobian_full_doubly_left + jacobian_derivative_full_doubly_left (src/jaxsim/rbda/jacobian.py:128-339), one
  * launch: out_J = [2*6*(6+n)][N] = B_J_full_WX_B (6 x (6+n), row-major) followed by B_Jdot_full_WX_B, both with
  * input and output in the base frame ("doubly left"); out_B_H_L = [nL*12][N] rows of [R|p] of every link

@@ -1,5 +1,6 @@
 """Namespace mirroring ``jaxsim.api`` for the step path: ``import jaxsim_amd.api as js``
 then ``js.model.step(model, data)``, ``js.data.JaxSimModelData.build(...)``,
-``js.contact.estimate_good_contact_parameters(...)``, ``js.ode.system_dynamics(model, data)``."""
+``js.contact.estimate_good_contact_parameters(...)``, ``js.ode.system_dynamics(model, data)``,
+``js.com.centroidal_momentum(model, data)``."""
 
-from . import contact, data, model, ode, references  # noqa: F401
+from . import com, contact, data, model, ode, references  # noqa: F401

@@ -655,3 +655,144 @@ def free_floating_bias_forces(model: JaxSimModel, data: JaxSimModelData):
         )
     fB, tau = inverse_dynamics(model, d)
     return np.concatenate([fB, tau], axis=-1)
+
+
+# ---- momentum and energy (src/jaxsim/api/model.py:888-925, 1988-2175, 2397-2453): one launch of the centroidal
+#      kernel (js.com, jxs_centroidal), cached on the data object, and the reference's 6x6 transforms on the host
+
+
+def link_spatial_inertia_matrices(model: JaxSimModel) -> np.ndarray:
+    """``link_spatial_inertia_matrices`` (``src/jaxsim/api/model.py:900-917``): [nL, 6, 6] in the link frames,
+    ``[[m 1, m S(c)^T], [m S(c), I_c + m S(c) S(c)^T]]`` (``math/inertia.py:14-41``), from the model tables."""
+    from .com import _skew
+
+    kdp = model.kin_dyn_parameters
+    m = np.asarray(kdp.link_mass, np.float64)[:, None, None]
+    S = _skew(np.asarray(kdp.link_com, np.float64))
+    M = np.zeros((m.shape[0], 6, 6))
+    M[:, :3, :3] = m * np.eye(3)
+    M[:, :3, 3:] = m * np.swapaxes(S, -1, -2)
+    M[:, 3:, :3] = m * S
+    M[:, 3:, 3:] = np.asarray(kdp.link_inertia_com, np.float64) + m * (S @ np.swapaxes(S, -1, -2))
+    return M
+
+
+def _repr_block(data: JaxSimModelData, rep) -> np.ndarray:
+    """``_mixed_to_repr_block`` for the representation ``rep``."""
+    with data.switch_velocity_representation(rep):
+        return _mixed_to_repr_block(data)
+
+
+def _force_shift(d: np.ndarray) -> np.ndarray:
+    """[N, 6, 6] force transform that moves the reference point of a wrench by -d (world axes): [f; n + d x f]."""
+    from .com import _skew
+
+    X = np.zeros(d.shape[:-1] + (6, 6))
+    X[..., :3, :3] = np.eye(3)
+    X[..., 3:, 3:] = np.eye(3)
+    X[..., 3:, :3] = _skew(d)
+    return X
+
+
+def total_momentum_jacobian(model: JaxSimModel, data: JaxSimModelData, *, output_vel_repr=None):
+    """``total_momentum_jacobian`` (``src/jaxsim/api/model.py:2024-2087``): ``free_floating_mass_matrix[0:6]`` with
+    the output in ``output_vel_repr`` (default: the data's), [6, 6+n] / [N, 6, 6+n].  From the centroidal momentum
+    matrix: moved from the CoM to the base position, then the 6x6 congruences of the mass matrix."""
+    from .com import COM, _centroidal
+
+    out_rep = data.velocity_representation if output_vel_repr is None else VelRepr(output_vel_repr)
+    rec, A_G = _centroidal(model, data, jacobian=True)
+    c = rec[:, COM : COM + 3] - data._base_transform_batched()[:, :3, 3]
+    Jh = _force_shift(c) @ A_G  # about the base position, world axes: frame C = the Mixed representation
+    Jh[:, :, :6] = Jh[:, :, :6] @ _mixed_to_repr_block(data)
+    Jh = np.swapaxes(_repr_block(data, out_rep), -1, -2) @ Jh
+    return data._out(Jh.astype(data.dtype))
+
+
+def locked_spatial_inertia(model: JaxSimModel, data: JaxSimModelData):
+    """``locked_spatial_inertia`` (``src/jaxsim/api/model.py:1993-2007``): ``total_momentum_jacobian[:, 0:6]``, from
+    the record alone (the locked centroidal inertia moved to the base position)."""
+    from .com import COM, _centroidal, _locked_G_world
+
+    rec, _ = _centroidal(model, data)
+    F = _force_shift(rec[:, COM : COM + 3] - data._base_transform_batched()[:, :3, 3])
+    X = _mixed_to_repr_block(data)
+    M = np.swapaxes(X, -1, -2) @ F @ _locked_G_world(model, data) @ np.swapaxes(F, -1, -2) @ X
+    return data._out(M.astype(data.dtype))
+
+
+def total_momentum(model: JaxSimModel, data: JaxSimModelData):
+    """``total_momentum`` (``src/jaxsim/api/model.py:2010-2021``): ``total_momentum_jacobian @ nu`` in the data's
+    representation, from the record (the centroidal momentum moved to the world origin, then to the data's frame)."""
+    from .com import COM, MOMENTUM, _centroidal
+
+    rec, _ = _centroidal(model, data)
+    h = rec[:, MOMENTUM : MOMENTUM + 6].copy()
+    h[:, 3:] += np.cross(rec[:, COM : COM + 3], h[:, :3])
+    h = _inertial_to_other(h, data.velocity_representation, data._base_transform_batched(), True)
+    return data._out(h.astype(data.dtype))
+
+
+def _avg_velocity_transform(model: JaxSimModel, data: JaxSimModelData, out_rep) -> np.ndarray:
+    """The motion transforms of ``average_velocity_jacobian`` (``src/jaxsim/api/model.py:2127-2157``): W_X_GW, B_X_GB or
+    BW_X_GW (translations), applied -- like the reference -- to the average centroidal velocity of the data's G frame."""
+    from .com import COM, _centroidal, _skew
+
+    rec, _ = _centroidal(model, data)
+    H = data._base_transform_batched()
+    p = rec[:, COM : COM + 3]
+    if out_rep == VelRepr.Body:
+        p = np.einsum("nji,nj->ni", H[:, :3, :3], p - H[:, :3, 3])
+    elif out_rep == VelRepr.Mixed:
+        p = p - H[:, :3, 3]
+    X = np.zeros(p.shape[:-1] + (6, 6))
+    X[:, :3, :3] = np.eye(3)
+    X[:, 3:, 3:] = np.eye(3)
+    X[:, :3, 3:] = _skew(p)
+    return X
+
+
+def average_velocity_jacobian(model: JaxSimModel, data: JaxSimModelData, *, output_vel_repr=None):
+    """``average_velocity_jacobian`` (``src/jaxsim/api/model.py:2108-2157``), [6, 6+n] / [N, 6, 6+n]."""
+    from . import com
+
+    out_rep = data.velocity_representation if output_vel_repr is None else VelRepr(output_vel_repr)
+    G_J = com.average_centroidal_velocity_jacobian(model, data)
+    G_J = np.asarray(G_J, np.float64).reshape(data.batch_size, 6, 6 + model.dofs())
+    return data._out((_avg_velocity_transform(model, data, out_rep) @ G_J).astype(data.dtype))
+
+
+def average_velocity(model: JaxSimModel, data: JaxSimModelData):
+    """``average_velocity`` (``src/jaxsim/api/model.py:2090-2105``): ``average_velocity_jacobian @ nu``, from the record."""
+    from . import com
+
+    v = np.asarray(com.average_centroidal_velocity(model, data), np.float64).reshape(data.batch_size, 6)
+    X = _avg_velocity_transform(model, data, data.velocity_representation)
+    return data._out(np.einsum("nij,nj->ni", X, v).astype(data.dtype))
+
+
+def kinetic_energy(model: JaxSimModel, data: JaxSimModelData):
+    """``kinetic_energy`` (``src/jaxsim/api/model.py:2415-2433``): 1/2 nu^T M nu (any representation)."""
+    from .com import KINETIC, _centroidal
+
+    rec, _ = _centroidal(model, data)
+    return data._out(rec[:, KINETIC].astype(data.dtype))
+
+
+def potential_energy(model: JaxSimModel, data: JaxSimModelData):
+    """``potential_energy`` (``src/jaxsim/api/model.py:2436-2453``) AS THE REFERENCE COMPUTES IT: ``m z_CoM gravity``
+    with ``model.gravity = -9.81``, i.e. ``-m g z`` -- NEGATIVE for a CoM above the ground.  So the physical potential
+    energy is ``-potential_energy`` and ``kinetic_energy - potential_energy`` is what a conservative motion keeps."""
+    from .com import POTENTIAL, _centroidal
+
+    rec, _ = _centroidal(model, data)
+    return data._out(rec[:, POTENTIAL].astype(data.dtype))
+
+
+def mechanical_energy(model: JaxSimModel, data: JaxSimModelData):
+    """``mechanical_energy`` (``src/jaxsim/api/model.py:2397-2412``): ``kinetic_energy + potential_energy`` like the
+    reference -- which, with the sign of its ``potential_energy``, is NOT conserved (``K - U`` is)."""
+    from .com import KINETIC, POTENTIAL, _centroidal
+
+    rec, _ = _centroidal(model, data)
+    return data._out((rec[:, KINETIC] + rec[:, POTENTIAL]).astype(data.dtype))

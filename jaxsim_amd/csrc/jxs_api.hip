@@ -25,6 +25,11 @@
 #include "jxs_params.h"
 #include "jxs_pack.h"
 
+static_assert(JXS_CENTROIDAL_COM == jxs::CR_COM && JXS_CENTROIDAL_MOMENTUM == jxs::CR_MOMENTUM && JXS_CENTROIDAL_INERTIA == jxs::CR_INERTIA &&
+                  JXS_CENTROIDAL_AVG_VEL == jxs::CR_AVG_VEL && JXS_CENTROIDAL_KINETIC == jxs::CR_KINETIC &&
+                  JXS_CENTROIDAL_POTENTIAL == jxs::CR_POTENTIAL && JXS_CENTROIDAL_MASS == jxs::CR_MASS && JXS_CENTROIDAL_ROWS == jxs::kCentRows,
+              "the record layout of include/jaxsim_amd.h and of the kernel (jxs_params.h CentroidalRow) differ");
+
 // kernels and launchers live in jxs_inst.hip (one translation unit per dtype and mode, jxs_kernels.h)
 namespace jxs_launch {
 template <typename T, int MODE>
@@ -89,6 +94,7 @@ hipError_t launch_mode(int mode, int G, const jxs::KParams<T>& P, const unsigned
     case jxs::MODE_GRAV: return launch_g<T, jxs::MODE_GRAV>(G, P, mblk, A, s);
     case jxs::MODE_DYN: return launch_g<T, jxs::MODE_DYN>(G, P, mblk, A, s);
     case jxs::MODE_DYN_RIGID: return launch_g<T, jxs::MODE_DYN_RIGID>(G, P, mblk, A, s);
+    case jxs::MODE_CENTROIDAL: return launch_g<T, jxs::MODE_CENTROIDAL>(G, P, mblk, A, s);
     default: return launch_g<T, jxs::MODE_KIN>(G, P, mblk, A, s);
   }
 }
@@ -889,6 +895,12 @@ int jxs_jacobian_full(jxs_model* model, const void* state, void* out_J, void* ou
   const size_t elems = (size_t)((N + lay.tile - 1) / lay.tile) * lay.tile * 12 * nv;
   JXS_HIP(hipMemsetAsync(out_J, 0, elems * (model->dtype == JXS_F64 ? 8 : 4), static_cast<hipStream_t>(stream)));
   return run_any(model, jxs::MODE_JAC, state, nullptr, nullptr, nullptr, 0, nullptr, out_J, out_B_H_L, nullptr, N, 1, stream);
+}
+int jxs_centroidal(jxs_model* model, const void* state, void* out_record, void* out_cmm, int N, void* stream) {
+  // [MODE_CENTROIDAL] record and A_G: every entry is written by the kernel (no memset), nothing is allocated and the host
+  // does not wait -- legal inside a stream capture
+  if (out_record == nullptr) return fail(JXS_EINVAL, "null out_record");
+  return run_any(model, jxs::MODE_CENTROIDAL, state, nullptr, nullptr, nullptr, 0, nullptr, out_cmm, out_record, nullptr, N, 1, stream);
 }
 int jxs_refresh_kinematics(jxs_model* model, const void* state, void* out_link_transforms, void* out_link_velocities,
                            int N, void* stream) {

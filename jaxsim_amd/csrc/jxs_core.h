@@ -769,6 +769,10 @@ struct Core {
       crba(lane, level, child, jrow, is_joint, is_root, MA, S6);
       return;
     }
+    if (MODE == MODE_CENTROIDAL) {
+      centroidal(lane, level, child, jrow, is_joint, is_root, MA, S6, vl, va, pB, doff, vBc, om);
+      return;
+    }
 
     V sdd = V(T(0));
     V acl[3], aca[3];  // base spatial acceleration in C incl. gravity (valid in every lane)
@@ -2743,6 +2747,178 @@ struct Core {
       for (int e = 0; e < 6; ++e) {
         ln.gstore(A.out_a, ck + e * nv, Fk[e], is_root, rows);
         ln.gstore(A.out_a, ck * nv + e, Fk[e], is_root, rows);
+      }
+    }
+  }
+
+  // ==========================================================================================
+  // Centroidal quantities (api/com.py; api/model.py:1988-2175, 2397-2453) in frame C.  One leaves-to-root sweep with the
+  // child gathers of crba() carries the composite inertia Ic (21), the subtree momentum h = sum M_i v_i (6) and twice the
+  // subtree kinetic energy sum v_i . M_i v_i (1).  The root lane then holds the locked inertia M_C and the total momentum
+  // h_C about the origin of C, and forms the record of include/jaxsim_amd.h (JXS_CENTROIDAL_*) from them:
+  //   c = first moment / m + doff   (the CoM as the cached link transforms place it, relative to the base position),
+  //   h_G = [h_lin ; h_ang - c x h_lin],   I_G = J_C - m (|c_t|^2 1 - c_t c_t^T) about the CoM c_t of the sweep,
+  //   average centroidal velocity = M_G^-1 h_G:  w = I_G^-1 (h_ang - c_t x h_lin),  v = h_lin / m - doff x w
+  // (M_G = X^T M_C X is diag(m 1, I_G) up to the base-link offset doff of quirk 12).  Like the reference the generalized
+  // velocity includes the stored base velocity of a fixed base (rbda/forward_kinematics.py:69-70), and U = m z g with the
+  // signed gravity P.g (api/model.py:2436-2453: a NEGATIVE potential energy for a CoM above the ground).
+  // out_a (optional): A_G in G[W], [6 * (6+n)][N] row-major; column 6 + j = [F_lin ; F_ang - c x F_lin] of joint j's lane
+  // (F = Ic S), the base block from the root lane -- every entry written, no per-column loop.
+  JXS_HD void centroidal(const VI& lane, const VI& level, const VI* child, const VI& jrow, const VM& is_joint,
+                         const VM& is_root, const V* M_link, const V* S6, const V* vl, const V* va, const V* pB,
+                         const V* doff, const V* vBc, const V* om) const {
+    const V zero = V(T(0));
+    V v6[6];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      v6[k] = P.floating ? vl[k] : vl[k] + vBc[k];
+      v6[3 + k] = P.floating ? va[k] : va[k] + om[k];
+    }
+    V Ic[21], h[6];
+#pragma unroll
+    for (int e = 0; e < 21; ++e) Ic[e] = M_link[e];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+      V acc = M_link[sidx(i, 0)] * v6[0];
+#pragma unroll
+      for (int j = 1; j < 6; ++j) acc = acc + M_link[sidx(i, j)] * v6[j];
+      h[i] = acc;
+    }
+    V ke2 = v6[0] * h[0];
+#pragma unroll
+    for (int i = 1; i < 6; ++i) ke2 = ke2 + v6[i] * h[i];
+    for (int Lv = P.max_depth; Lv >= 1; --Lv) {
+      const VM is_par = level == (Lv - 1);
+      const int nch = P.maxch(Lv);
+      if (nch >= 1) {
+        const VM ok0 = is_par && (child[0] >= 0);
+        V s9[9];
+#pragma unroll
+        for (int e = 0; e < 9; ++e) s9[e] = Ic[e];
+        add_from_next<9>(lane, Ic, s9, ok0);
+#pragma unroll
+        for (int e = 0; e < 9; ++e) s9[e] = Ic[9 + e];
+        add_from_next<9>(lane, Ic + 9, s9, ok0);
+        V a9[9];
+#pragma unroll
+        for (int e = 0; e < 3; ++e) a9[e] = Ic[18 + e];
+#pragma unroll
+        for (int e = 0; e < 6; ++e) a9[3 + e] = h[e];
+#pragma unroll
+        for (int e = 0; e < 9; ++e) s9[e] = a9[e];
+        add_from_next<9>(lane, a9, s9, ok0);
+#pragma unroll
+        for (int e = 0; e < 3; ++e) Ic[18 + e] = a9[e];
+#pragma unroll
+        for (int e = 0; e < 6; ++e) h[e] = a9[3 + e];
+        ke2 = ke2 + vsel(ok0, ln.from_next(ke2), zero);
+      }
+#pragma unroll
+      for (int k = 1; k < kMaxChildren; ++k) {
+        if (k >= P.max_children) break;  // (the widest link of the MODEL: a constant of a model-specialised kernel)
+        if (k < nch) {
+          const V okf = vsel(is_par && (child[k] >= 0), V(T(1)), zero);
+          V g[28];
+#pragma unroll
+          for (int e = 0; e < 21; ++e) g[e] = ln.shfl(Ic[e], child[k]);
+#pragma unroll
+          for (int e = 0; e < 6; ++e) g[21 + e] = ln.shfl(h[e], child[k]);
+          g[27] = ln.shfl(ke2, child[k]);
+          ln.fence();
+#pragma unroll
+          for (int e = 0; e < 21; ++e) Ic[e] = Ic[e] + okf * g[e];
+#pragma unroll
+          for (int e = 0; e < 6; ++e) h[e] = h[e] + okf * g[21 + e];
+          ke2 = ke2 + okf * g[27];
+        }
+      }
+    }
+    // ---- root lane: mass, CoM, centroidal momentum and inertia, average velocity, energies
+    const V m = Ic[sidx(0, 0)];
+    const VM has_m = m > zero;
+    const V inv_m = vsel(has_m, vrcp_acc(vsel(has_m, m, V(T(1)))), zero);
+    const V mc[3] = {Ic[sidx(1, 5)], -Ic[sidx(0, 5)], Ic[sidx(0, 4)]};  // first moment: the block m S(c)^T of M_C
+    V ct[3], c[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) ct[k] = mc[k] * inv_m, c[k] = ct[k] + doff[k];
+    V IG[6];  // xx, xy, xz, yy, yz, zz about the CoM c_t
+    IG[0] = Ic[sidx(3, 3)] - (mc[1] * ct[1] + mc[2] * ct[2]);
+    IG[1] = Ic[sidx(3, 4)] + mc[0] * ct[1];
+    IG[2] = Ic[sidx(3, 5)] + mc[0] * ct[2];
+    IG[3] = Ic[sidx(4, 4)] - (mc[0] * ct[0] + mc[2] * ct[2]);
+    IG[4] = Ic[sidx(4, 5)] + mc[1] * ct[2];
+    IG[5] = Ic[sidx(5, 5)] - (mc[0] * ct[0] + mc[1] * ct[1]);
+    V hG[6], Lt[3], t[3];
+    cross(c, h, t);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) hG[k] = h[k], hG[3 + k] = h[3 + k] - t[k];
+    cross(ct, h, t);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) Lt[k] = h[3 + k] - t[k];  // angular momentum about c_t
+    // w = I_G^-1 Lt (adjugate of the symmetric 3x3 on the root lane)
+    const V A00 = IG[3] * IG[5] - IG[4] * IG[4], A01 = IG[2] * IG[4] - IG[1] * IG[5], A02 = IG[1] * IG[4] - IG[2] * IG[3];
+    const V A11 = IG[0] * IG[5] - IG[2] * IG[2], A12 = IG[1] * IG[2] - IG[0] * IG[4], A22 = IG[0] * IG[3] - IG[1] * IG[1];
+    const V det = IG[0] * A00 + IG[1] * A01 + IG[2] * A02;
+    const VM has_det = vabs(det) > zero;
+    const V inv_det = vsel(has_det, vrcp_acc(vsel(has_det, det, V(T(1)))), zero);
+    V w[3], vG[3];
+    w[0] = (A00 * Lt[0] + A01 * Lt[1] + A02 * Lt[2]) * inv_det;
+    w[1] = (A01 * Lt[0] + A11 * Lt[1] + A12 * Lt[2]) * inv_det;
+    w[2] = (A02 * Lt[0] + A12 * Lt[1] + A22 * Lt[2]) * inv_det;
+    cross(doff, w, t);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) vG[k] = h[k] * inv_m - t[k];
+    const VI zl = lane * 0;
+    constexpr int R = kCentRows;
+    if (A.out_H != nullptr) {
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        ln.gstore(A.out_H, zl + (CR_COM + k), pB[k] + c[k], is_root, R);
+        ln.gstore(A.out_H, zl + (CR_AVG_VEL + k), vG[k], is_root, R);
+        ln.gstore(A.out_H, zl + (CR_AVG_VEL + 3 + k), w[k], is_root, R);
+      }
+#pragma unroll
+      for (int k = 0; k < 6; ++k) {
+        ln.gstore(A.out_H, zl + (CR_MOMENTUM + k), hG[k], is_root, R);
+        ln.gstore(A.out_H, zl + (CR_INERTIA + k), IG[k], is_root, R);
+      }
+      ln.gstore(A.out_H, zl + CR_KINETIC, V(T(0.5)) * ke2, is_root, R);
+      ln.gstore(A.out_H, zl + CR_POTENTIAL, m * (pB[2] + c[2]) * V(P.g), is_root, R);
+      ln.gstore(A.out_H, zl + CR_MASS, m, is_root, R);
+    }
+    if (A.out_a == nullptr) return;
+    const int nv = 6 + P.n, rows = 6 * nv;
+    V cb[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) cb[k] = ln.shfl(c[k], zl);
+    ln.fence();
+    // joint lanes: column 6 + jrow
+    {
+      V F[6];
+#pragma unroll
+      for (int i = 0; i < 6; ++i) {
+        V acc = Ic[sidx(i, 0)] * S6[0];
+#pragma unroll
+        for (int j = 1; j < 6; ++j) acc = acc + Ic[sidx(i, j)] * S6[j];
+        F[i] = acc;
+      }
+      cross(cb, F, t);
+      const VI col = vsel(is_joint, jrow + 6, zl);
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+        ln.gstore(A.out_a, i * nv + col, F[i], is_joint, rows);
+        ln.gstore(A.out_a, (3 + i) * nv + col, F[3 + i] - t[i], is_joint, rows);
+      }
+    }
+    // root lane: the base block X^T M_C (column j = [M_lin,j ; M_ang,j - c x M_lin,j])
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+      const V ml[3] = {Ic[sidx(0, j)], Ic[sidx(1, j)], Ic[sidx(2, j)]};
+      cross(c, ml, t);
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+        ln.gstore(A.out_a, zl + (i * nv + j), ml[i], is_root, rows);
+        ln.gstore(A.out_a, zl + ((3 + i) * nv + j), Ic[sidx(3 + i, j)] - t[i], is_root, rows);
       }
     }
   }

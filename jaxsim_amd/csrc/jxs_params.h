@@ -237,9 +237,24 @@ enum Mode : int {
   // state DERIVATIVE in the layout of the state block (KArgs::state_out: pdot_B, Qdot, sdot, W_vdot_WB, sddot, mdot) and,
   // on request, the inertial 6D contact wrench of every link (KArgs::out_H, [nL * 6][N]).
   MODE_DYN = 12,        // SoftContacts / no collidable points
-  MODE_DYN_RIGID = 13   // RigidContacts / RelaxedRigidContacts (contact forces solved like stage 0 of the step, no impact)
+  MODE_DYN_RIGID = 13,  // RigidContacts / RelaxedRigidContacts (contact forces solved like stage 0 of the step, no impact)
+  // centroidal momentum, CoM and energies (api/com.py, api/model.py:1988-2175, 2397-2453): one leaves-to-root sweep of the
+  // composite inertia, the subtree momentum and the subtree kinetic energy; a record per environment (KArgs::out_H,
+  // include/jaxsim_amd.h JXS_CENTROIDAL_*) and, on request, the centroidal momentum matrix A_G in G[W] (KArgs::out_a)
+  MODE_CENTROIDAL = 14
 };
-constexpr int kNumModes = 14;
+constexpr int kNumModes = 15;
+// MODE_CENTROIDAL: rows of the per-environment record (include/jaxsim_amd.h JXS_CENTROIDAL_*, checked there by jxs_api.hip)
+enum CentroidalRow : int {
+  CR_COM = 0,         // 3: W_p_CoM
+  CR_MOMENTUM = 3,    // 6: centroidal momentum h_G in G[W] (linear; angular about the CoM)
+  CR_INERTIA = 9,     // 6: rotational inertia I_G about the CoM, world axes: xx, xy, xz, yy, yz, zz
+  CR_AVG_VEL = 15,    // 6: average centroidal velocity in G[W] (linear; angular)
+  CR_KINETIC = 21,    // 1: kinetic energy
+  CR_POTENTIAL = 22,  // 1: potential energy as the reference computes it, m z_CoM g with g = -9.81 (api/model.py:2436-2453)
+  CR_MASS = 23,       // 1: total mass
+  kCentRows = 24
+};
 
 enum ForceRepr : int { REPR_INERTIAL = 0, REPR_BODY = 1, REPR_MIXED = 2 };  // api/common.py:39-47
 
@@ -353,6 +368,7 @@ struct KArgs {
   const T* in_a;       // MODE_ID: [6+n][N] inertial base acceleration + joint accelerations, or null
   T* out_a;            // MODE_FD: [6+n][N] ; MODE_ID: [6+n][N] (base wrench, joint torques)
   T* out_H;            // MODE_KIN: [nL*12][N] rows of [R|p] per link (row-major 3x4); MODE_DYN*: [nL*6][N] inertial link contact wrenches, or null
+                       // MODE_CENTROIDAL: [JXS_CENTROIDAL_ROWS][N] record (out_a: [6*(6+n)][N] centroidal momentum matrix, or null)
   T* out_V;            // MODE_KIN: [nL*6][N] inertial-fixed link velocities
   int N;               // batch size (leading dimension of every [row][N] array)
   int n_steps;         // MODE_STEP: consecutive steps fused in this launch (state carried in registers)

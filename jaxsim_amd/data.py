@@ -66,6 +66,7 @@ class JaxSimModelData:
         self._batched = bool(batched)
         self._host = None  # lazily downloaded dict of [N,...] arrays
         self._kin = None  # lazily computed (link_transforms, link_velocities)
+        self._cent = None  # lazily computed centroidal record and momentum matrix (api/com.py)
 
     # -- construction -----------------------------------------------------------------------
     @staticmethod
@@ -186,6 +187,7 @@ class JaxSimModelData:
         """The device buffer was overwritten (``step(..., inplace=True)``): forget the host copies."""
         self._host = None
         self._kin = None
+        self._cent = None
 
     def _fields(self) -> dict:
         if self._host is None:

@@ -190,8 +190,9 @@ def _compile_locked(text: str, fields: dict, assign: str, out: pathlib.Path) -> 
     return out
 
 
-# forward dynamics, inverse dynamics, cached kinematics, mass matrix, Jacobians, mass-matrix inverse, gravity torques: on request
-QUERY_MODES = (1, 2, 3, 8, 9, 10, 11)
+# forward dynamics, inverse dynamics, cached kinematics, mass matrix, Jacobians, mass-matrix inverse, gravity torques,
+# centroidal quantities (js.com): on request
+QUERY_MODES = (1, 2, 3, 8, 9, 10, 11, 14)
 
 
 def attach(dm, model, mode: int | None = None, *, build: bool = False, require: bool = False) -> bool:
@@ -240,6 +241,7 @@ def attach(dm, model, mode: int | None = None, *, build: bool = False, require: 
 
 
 MODE_GRAV = 11
+MODE_CENTROIDAL = 14
 
 
 def ensure_mode(dm, model, mode: int) -> bool:

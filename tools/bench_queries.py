@@ -2,7 +2,8 @@
 """[round 4] The query kernels of SURVEY section 8 rows F / R / N / f4 timed the way the reference times them
 (`tests/test_benchmark.py:39-152`: one function per benchmark, batch of states, `jax.block_until_ready`): forward
 dynamics (ABA), bias forces (RNEA at zero acceleration), inverse dynamics, gravity torques, forward kinematics,
-mass matrix (CRBA), mass-matrix inverse, the full Jacobian + its derivative -- and the step kernels beside them.
+mass matrix (CRBA), mass-matrix inverse, the full Jacobian + its derivative, the centroidal record (with and without the
+centroidal momentum matrix, beside the CRBA + kinematics launches it replaces) -- and the step kernels beside them.
 State resident in HBM, HIP events on the launch stream around `--reps` launches, the 24-link humanoid of the
 headline (`bench.build_model`), both precisions.  Per launch: time, batch / time, and the HBM bytes the launch has
 to move (state in + result out, algorithmic) against 8 TB/s.
@@ -60,6 +61,7 @@ for dtype in (np.float32, np.float64):
     sp = C.c_void_p(data._state.ptr)
     acc, frc, tau, M, Mi, J, HT, HV = buf(nv), buf(nv), buf(n), buf(nv * nv), buf(nv * nv), buf(2 * 6 * nv), buf(nL * 12), buf(nL * 6)
     scratch = buf(rows_state)
+    CR, AG = buf(24), buf(6 * nv)  # centroidal record (JXS_CENTROIDAL_ROWS) and momentum matrix
     cases = [
         ("forward_dynamics_aba (MODE_FD)", lambda: lib.jxs_forward_dynamics_aba(dm.handle, sp, None, None, 2, acc, N, stream.handle), rows_state + nv),
         ("free_floating_bias_forces (MODE_ID, zero acc.)", lambda: lib.jxs_inverse_dynamics(dm.handle, sp, None, None, 2, frc, N, stream.handle), rows_state + nv),
@@ -69,6 +71,11 @@ for dtype in (np.float32, np.float64):
         ("free_floating_mass_matrix (MODE_CRBA)", lambda: lib.jxs_mass_matrix(dm.handle, sp, M, N, stream.handle), rows_state + nv * nv),
         ("free_floating_mass_matrix_inverse (MODE_MINV)", lambda: lib.jxs_mass_matrix_inverse(dm.handle, sp, Mi, N, stream.handle), rows_state + nv * nv),
         ("jacobian_full + derivative (MODE_JAC)", lambda: lib.jxs_jacobian_full(dm.handle, sp, J, HT, N, stream.handle), rows_state + 2 * 6 * nv + nL * 12),
+        ("centroidal record (MODE_CENTROIDAL)", lambda: lib.jxs_centroidal(dm.handle, sp, CR, None, N, stream.handle), rows_state + 24),
+        ("centroidal record + A_G (MODE_CENTROIDAL)", lambda: lib.jxs_centroidal(dm.handle, sp, CR, AG, N, stream.handle), rows_state + 24 + 6 * nv),
+        ("CRBA + kinematics (what MODE_CENTROIDAL replaces)",
+         lambda: lib.jxs_mass_matrix(dm.handle, sp, M, N, stream.handle) or lib.jxs_refresh_kinematics(dm.handle, sp, HT, HV, N, stream.handle),
+         2 * rows_state + nv * nv + nL * 18),
         ("step, out of place (MODE_STEP)", lambda: lib.jxs_step(dm.handle, sp, scratch, None, None, 2, N, stream.handle), 2 * rows_state),
     ]
     for name, call, rows_moved in cases:
