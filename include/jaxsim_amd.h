@@ -349,6 +349,36 @@ int jxs_mass_matrix_inverse(jxs_model* model, const void* state, void* out_Minv,
 #define JXS_CENTROIDAL_ROWS 24
 int jxs_centroidal(jxs_model* model, const void* state, void* out_record, void* out_cmm, int N, void* stream);
 
+/* Frames: poses, velocities, bias accelerations and Jacobians of frames rigidly attached to links, one launch
+ * (jaxsim.api.link: transform, velocity, jacobian, bias_acceleration; jaxsim.api.frame: transform, velocity, jacobian;
+ * jaxsim.api.model.link_bias_accelerations, src/jaxsim/api/model.py:2179-2395).  A target is (parent link L, L_H_F); a
+ * link is the target (L, identity).  The link bias accelerations are one ancestor prefix sum of v_i x vJ_i at zero joint
+ * acceleration, started from the zero base acceleration of the INPUT representation converted to inertial-fixed.
+ * jxs_frames_create uploads an immutable target table (refused with JXS_EINVAL: n < 1, n > JXS_FRAME_MAX_TARGETS, a
+ * parent outside [0, nL), a last row of L_H_F other than [0 0 0 1]); one table serves every launch and stream of its
+ * model, and one specialised MODE_FRAMES kernel serves every table.
+ * jxs_frame_kinematics, for the generalized velocity in representation in_repr (I) and outputs in out_repr (O), both
+ * JXS_REPR_* (0 Inertial, 1 Body, 2 Mixed):
+ *   out_record = [n * JXS_FRAME_ROWS][N], target t at rows t * JXS_FRAME_ROWS + ...:
+ *     rows  0..11  JXS_FRAME_POSE  W_H_F as [R|p], 3 x 4 row-major (the pose of the cached link kinematics)
+ *     rows 12..17  JXS_FRAME_VEL   O_v_WF = O_J_WF_I I_nu
+ *     rows 18..23  JXS_FRAME_BIAS  O_vdot_bias_WF = O_Jdot_WF_I I_nu (for a link and I = O: link_bias_accelerations)
+ *   out_J = [n * 6 * (6+n_joints)][N] or NULL: O_J_WF_I of target t, row r, column c at row index
+ *     (t * 6 + r) * (6+n_joints) + c; exact zeros in the columns of the joints that do not support L.
+ * As in the reference, the stored base velocity of a fixed-base model is part of the generalized velocity.  Every entry of
+ * both outputs is written by the kernel: no allocation, no memset, no host synchronisation (legal inside a stream
+ * capture).                                                                                        */
+#define JXS_FRAME_POSE 0
+#define JXS_FRAME_VEL 12
+#define JXS_FRAME_BIAS 18
+#define JXS_FRAME_ROWS 24
+#define JXS_FRAME_MAX_TARGETS 4096
+typedef struct jxs_frames jxs_frames;
+int jxs_frames_create(jxs_model* model, int n, const int32_t* parent_link, const double* L_H_F /* [n][16] */, jxs_frames** out);
+int jxs_frames_destroy(jxs_frames* frames);
+int jxs_frame_kinematics(jxs_model* model, const jxs_frames* frames, const void* state, int in_repr, int out_repr,
+                         void* out_record, void* out_J, int N, void* stream);
+
 /* jacobian_full_doubly_left + jacobian_derivative_full_doubly_left (src/jaxsim/rbda/jacobian.py:128-339), one
  * launch: out_J = [2*6*(6+n)][N] = B_J_full_WX_B (6 x (6+n), row-major) followed by B_Jdot_full_WX_B, both with
  * input and output in the base frame ("doubly left"); out_B_H_L = [nL*12][N] rows of [R|p] of every link

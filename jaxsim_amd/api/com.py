@@ -6,7 +6,8 @@ rotational inertia about the CoM, average centroidal velocity, kinetic and poten
 the centroidal momentum matrix ``A_G`` in G[W] for a Mixed generalized velocity.  The reference's frame conventions
 are applied on the host, on [N, 6] / [N, 6, 6+n] arrays: G[W] for Inertial and Mixed data, G[B] = (W_p_CoM, base axes)
 for Body data.  The host copy of the record is cached on the data object (like its link kinematics): ``com_position``
-followed by ``centroidal_momentum`` on the same state is one launch.  Not covered: ``bias_acceleration``.
+followed by ``centroidal_momentum`` on the same state is one launch.  ``bias_acceleration`` is composed from the
+all-links record of the frame kernel (``api/frame.py``) in Body representation and the link inertias.
 """
 
 from __future__ import annotations
@@ -167,3 +168,25 @@ def com_linear_velocity(model, data):
     """``com_linear_velocity`` (``src/jaxsim/api/com.py:54-81``): the linear part of the average centroidal velocity."""
     rec, _ = _centroidal(model, data)
     return data._out(_to_G_frame(data, rec[:, AVG_VEL : AVG_VEL + 6])[:, :3].astype(data.dtype))
+
+
+def bias_acceleration(model, data):
+    """``bias_acceleration`` (``src/jaxsim/api/com.py:251-421``): the bias linear acceleration of the CoM, [3] / [N, 3], in
+    G[W] (Inertial / Mixed data) or G[B] (Body).  The body-fixed link bias accelerations and velocities of the all-links
+    record of the frame kernel (input in the data's representation, output Body) give the bias momentum rate
+    sum_L W_Xf_L (M_L a_L + v_L x* M_L v_L), whose linear part divided by the mass is the result."""
+    from . import frame as _frame
+    from .model import link_spatial_inertia_matrices
+
+    rec, _ = _frame._record(model, data, _frame._ALL_LINKS, VelRepr.Body)
+    M = np.asarray(link_spatial_inertia_matrices(model), dtype=np.float64)  # [nL, 6, 6]
+    a = rec[:, :, _frame.BIAS : _frame.BIAS + 6]
+    v = rec[:, :, _frame.VEL : _frame.VEL + 6]
+    R = rec[:, :, _frame.POSE : _frame.POSE + 12].reshape(rec.shape[:2] + (3, 4))[..., :3]
+    Ma, Mv = np.einsum("lij,nlj->nli", M, a), np.einsum("lij,nlj->nli", M, v)
+    f_lin = Ma[..., :3] + np.cross(v[..., 3:], Mv[..., :3])  # linear part of M a + v x* M v
+    h_lin = np.einsum("nlij,nlj->ni", R, f_lin)
+    acc = h_lin / float(np.sum(model.kin_dyn_parameters.link_mass))
+    if data.velocity_representation == VelRepr.Body:
+        acc = np.einsum("nji,nj->ni", data._base_transform_batched()[:, :3, :3], acc)
+    return data._out(acc.astype(data.dtype))

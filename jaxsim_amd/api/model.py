@@ -796,3 +796,19 @@ def mechanical_energy(model: JaxSimModel, data: JaxSimModelData):
 
     rec, _ = _centroidal(model, data)
     return data._out((rec[:, KINETIC] + rec[:, POTENTIAL]).astype(data.dtype))
+
+
+def link_bias_accelerations(model: JaxSimModel, data: JaxSimModelData) -> np.ndarray:
+    """``link_bias_accelerations`` (``src/jaxsim/api/model.py:2179-2395``): ``J̇ν`` of every link in the data's velocity
+    representation, [nL, 6] / [N, nL, 6] -- one launch of the frame kernel over all links (``api/frame.py``), shared with
+    ``js.link.transform`` / ``velocity`` / ``bias_acceleration`` of the same state."""
+    from . import frame as _frame
+
+    rec, _ = _frame._record(model, data, _frame._ALL_LINKS, data.velocity_representation)
+    return data._out(rec[:, :, _frame.BIAS : _frame.BIAS + 6].astype(data.dtype))
+
+
+def forward_kinematics(model: JaxSimModel, data: JaxSimModelData) -> np.ndarray:
+    """``forward_kinematics`` (``src/jaxsim/api/model.py:474-493``): ``W_H_L`` of all links, [nL, 4, 4] / [N, nL, 4, 4],
+    from the cached kinematics (the kinematics kernel, ``MODE_KIN``)."""
+    return data._link_transforms

@@ -20,6 +20,7 @@
 #include <memory>
 #include <mutex>
 #include <string>
+#include <type_traits>
 
 #include "../../include/jaxsim_amd.h"
 #include "jxs_params.h"
@@ -29,6 +30,10 @@ static_assert(JXS_CENTROIDAL_COM == jxs::CR_COM && JXS_CENTROIDAL_MOMENTUM == jx
                   JXS_CENTROIDAL_AVG_VEL == jxs::CR_AVG_VEL && JXS_CENTROIDAL_KINETIC == jxs::CR_KINETIC &&
                   JXS_CENTROIDAL_POTENTIAL == jxs::CR_POTENTIAL && JXS_CENTROIDAL_MASS == jxs::CR_MASS && JXS_CENTROIDAL_ROWS == jxs::kCentRows,
               "the record layout of include/jaxsim_amd.h and of the kernel (jxs_params.h CentroidalRow) differ");
+
+static_assert(JXS_FRAME_POSE == jxs::FR_POSE && JXS_FRAME_VEL == jxs::FR_VEL && JXS_FRAME_BIAS == jxs::FR_BIAS &&
+                  JXS_FRAME_ROWS == jxs::kFrameRows && JXS_FRAME_MAX_TARGETS == jxs::kMaxFrameTargets,
+              "the frame record layout of include/jaxsim_amd.h and of the kernel (jxs_params.h FR_*) differ");
 
 // kernels and launchers live in jxs_inst.hip (one translation unit per dtype and mode, jxs_kernels.h)
 namespace jxs_launch {
@@ -95,6 +100,7 @@ hipError_t launch_mode(int mode, int G, const jxs::KParams<T>& P, const unsigned
     case jxs::MODE_DYN: return launch_g<T, jxs::MODE_DYN>(G, P, mblk, A, s);
     case jxs::MODE_DYN_RIGID: return launch_g<T, jxs::MODE_DYN_RIGID>(G, P, mblk, A, s);
     case jxs::MODE_CENTROIDAL: return launch_g<T, jxs::MODE_CENTROIDAL>(G, P, mblk, A, s);
+    case jxs::MODE_FRAMES: return launch_g<T, jxs::MODE_FRAMES>(G, P, mblk, A, s);
     default: return launch_g<T, jxs::MODE_KIN>(G, P, mblk, A, s);
   }
 }
@@ -102,6 +108,7 @@ hipError_t launch_mode(int mode, int G, const jxs::KParams<T>& P, const unsigned
 // Host tables of one model + its device model block (jxs_params.h: KParams | ltf | lti | rti | point chunks)
 template <typename T>
 struct ModelT {
+  using value_type = T;
   jxs::Packed<T> pk;
   unsigned char* mblk = nullptr;
   // model-specialised kernels (jxs_model_attach_specialized): launch entry per mode, null = generic kernel
@@ -142,6 +149,13 @@ struct ModelT {
 };
 
 }  // namespace
+
+// an immutable target table on the device (jxs_frames_create): parent lane, parent link and L_H_F of every target
+struct jxs_frames {
+  const jxs_model* owner = nullptr;
+  int n = 0;
+  void* tgt = nullptr;  // [n][jxs::kTgtStride] in the precision of the owner
+};
 
 struct jxs_model {
   unsigned long long uid = 0;  // unique per created model: cached launch graphs are keyed by it, not by the address
@@ -901,6 +915,89 @@ int jxs_centroidal(jxs_model* model, const void* state, void* out_record, void* 
   // does not wait -- legal inside a stream capture
   if (out_record == nullptr) return fail(JXS_EINVAL, "null out_record");
   return run_any(model, jxs::MODE_CENTROIDAL, state, nullptr, nullptr, nullptr, 0, nullptr, out_cmm, out_record, nullptr, N, 1, stream);
+}
+int jxs_frames_create(jxs_model* model, int n, const int32_t* parent_link, const double* L_H_F, jxs_frames** out) {
+  if (out == nullptr) return fail(JXS_EINVAL, "null out");
+  *out = nullptr;
+  if (model == nullptr) return fail(JXS_EINVAL, "null model");
+  if (n < 1 || n > JXS_FRAME_MAX_TARGETS)
+    return fail(JXS_EINVAL, "number of frame targets " + std::to_string(n) + " outside [1, " + std::to_string(JXS_FRAME_MAX_TARGETS) + "]");
+  if (parent_link == nullptr || L_H_F == nullptr) return fail(JXS_EINVAL, "null parent_link or L_H_F");
+  auto make = [&](auto* mt) -> int {
+    using T = typename std::remove_pointer_t<decltype(mt)>::value_type;
+    const auto& pk = mt->pk;
+    const int nL = pk.P.nL;
+    std::vector<int> lane_of(nL, -1);
+    for (int l = 0; l < pk.G; ++l) {
+      const int link = pk.lti[l * jxs::kLtiStride + jxs::LI_LINK];
+      if (link >= 0 && link < nL) lane_of[link] = l;
+    }
+    std::vector<T> tbl((size_t)n * jxs::kTgtStride, T(0));
+    for (int t = 0; t < n; ++t) {
+      const int L = parent_link[t];
+      if (L < 0 || L >= nL)
+        return fail(JXS_EINVAL, "frame target " + std::to_string(t) + ": parent link " + std::to_string(L) + " outside [0, " + std::to_string(nL) + ")");
+      const double* H = L_H_F + 16 * (size_t)t;
+      if (H[12] != 0.0 || H[13] != 0.0 || H[14] != 0.0 || H[15] != 1.0)
+        return fail(JXS_EINVAL, "frame target " + std::to_string(t) + ": the last row of L_H_F is not [0 0 0 1]");
+      T* r = tbl.data() + (size_t)t * jxs::kTgtStride;
+      r[jxs::TG_LANE] = static_cast<T>(lane_of[L]);
+      r[jxs::TG_LINK] = static_cast<T>(L);
+      for (int i = 0; i < 3; ++i) {
+        for (int j = 0; j < 3; ++j) r[jxs::TG_R + 3 * i + j] = static_cast<T>(H[4 * i + j]);
+        r[jxs::TG_P + i] = static_cast<T>(H[4 * i + 3]);
+      }
+    }
+    auto f = std::make_unique<jxs_frames>();
+    f->owner = model;
+    f->n = n;
+    JXS_HIP(hipMalloc(&f->tgt, tbl.size() * sizeof(T)));
+    hipError_t e = hipMemcpy(f->tgt, tbl.data(), tbl.size() * sizeof(T), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+      (void)hipFree(f->tgt);
+      return hip_fail(e, "uploading the frame targets");
+    }
+    *out = f.release();
+    return JXS_OK;
+  };
+  return model->dtype == JXS_F64 ? make(model->f64.get()) : make(model->f32.get());
+}
+int jxs_frames_destroy(jxs_frames* frames) {
+  if (frames == nullptr) return JXS_OK;
+  (void)hipFree(frames->tgt);  // (hipFree waits for the launches that may still read the table)
+  delete frames;
+  return JXS_OK;
+}
+int jxs_frame_kinematics(jxs_model* model, const jxs_frames* frames, const void* state, int in_repr, int out_repr,
+                         void* out_record, void* out_J, int N, void* stream) {
+  // [MODE_FRAMES] every entry of both outputs is written by the kernel (no memset), nothing is allocated and the host does
+  // not wait -- legal inside a stream capture
+  if (model == nullptr) return fail(JXS_EINVAL, "null model");
+  if (frames == nullptr) return fail(JXS_EINVAL, "null frames");
+  if (frames->owner != model) return fail(JXS_EINVAL, "the frame targets were created for another model");
+  if (state == nullptr) return fail(JXS_EINVAL, "null state");
+  if (out_record == nullptr) return fail(JXS_EINVAL, "null out_record");
+  if (N <= 0) return fail(JXS_EINVAL, "N must be positive");
+  if (in_repr < 0 || in_repr > 2 || out_repr < 0 || out_repr > 2) return fail(JXS_EINVAL, "invalid velocity representation");
+  auto go = [&](auto* mt) -> int {
+    using T = typename std::remove_pointer_t<decltype(mt)>::value_type;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    jxs::KArgs<T> a = mt->args(N);
+    a.state_in = static_cast<const T*>(state);
+    a.out_H = static_cast<T*>(out_record);
+    a.out_a = static_cast<T*>(out_J);
+    a.tgt = static_cast<const T*>(frames->tgt);
+    a.n_tgt = frames->n;
+    a.in_repr = in_repr;
+    a.out_repr = out_repr;
+    a.n_steps = 1;
+    const int mode = jxs::MODE_FRAMES;
+    hipError_t e = mt->spec_launch[mode] != nullptr ? static_cast<hipError_t>(mt->spec_launch[mode](&mt->pk.P, mt->mblk, &a, s))
+                                                    : launch_mode<T>(mode, mt->pk.G, mt->pk.P, mt->mblk, a, s);
+    if (e != hipSuccess) return hip_fail(e, "kernel launch");
+    return JXS_OK;
+  };
+  return model->dtype == JXS_F64 ? go(model->f64.get()) : go(model->f32.get());
 }
 int jxs_refresh_kinematics(jxs_model* model, const void* state, void* out_link_transforms, void* out_link_velocities,
                            int N, void* stream) {

@@ -506,6 +506,10 @@ struct Core {
       jacobians(lane, lnk, level, jrow, is_joint, is_root, R0, R, r, Sl, Sa, vl, va, vBc, om);
       return;
     }
+    if (MODE == MODE_FRAMES) {
+      frames(lane, level, jump, jrow, is_joint, is_root, R0, R, r, Sl, Sa, vJl, vJa, vl, va, pB, doff, vBc, om);
+      return;
+    }
     if (MODE == MODE_GRAV) {
       gravity_torques(lane, jrow, level, child, is_joint, R, r, cL, mass, Sl, Sa);
       return;
@@ -3030,6 +3034,190 @@ struct Core {
         ln.gstore(A.out_H, lnk * 12 + (4 * i + 1), b1[i], is_link, P.nL * 12);
         ln.gstore(A.out_H, lnk * 12 + (4 * i + 2), b2[i], is_link, P.nL * 12);
         ln.gstore(A.out_H, lnk * 12 + (4 * i + 3), bp[i], is_link, P.nL * 12);
+      }
+    }
+  }
+
+  // ==========================================================================================
+  // Frames (api/link.py, api/frame.py; api/model.py:2179-2395 link_bias_accelerations).  Every spatial vector below is
+  // in frame C (origin at the base position, world axes), the tree placed like ABA places it (no base-link offset).
+  //   v_i   full link velocity: the stored base velocity is part of it for a fixed base too (the reference's
+  //         link_bias_accelerations and free-floating Jacobians read data.base_velocity whatever the base);
+  //   a_i   intrinsic link acceleration at zero joint acceleration and zero INPUT-representation base acceleration,
+  //         a_i = a_lambda(i) + v_i x vJ_i (an ancestor prefix sum); a_base = C_X_W W_vdot_WB with W_vdot_WB the zero
+  //         acceleration of the input representation converted to inertial-fixed (api/model.py:2203-2260): zero for
+  //         Inertial and Body, [pdot_B x w_B ; 0] for Mixed.
+  // A target F = (parent link L, L_H_F) is rigidly attached to L: it moves with v_L and a_L.  Its outputs in the output
+  // representation O (api/model.py:2345-2387 body_to_other_representation, frame.py:240-315):
+  //   Inertial  W_X_F:  [x_lin + P x x_ang ; x_ang],  P = p_B + doff (the pose of the cached kinematics)
+  //   Body      F_X_C:  R_F^T [x_lin - p_F x x_ang ; x_ang]
+  //   Mixed     FW_X_C: [x_lin - p_F x x_ang ; x_ang]  (+ [w_F x pdot_F ; 0] for the acceleration)
+  // with R_F = R_L R_LF, p_F = r_L + R_L p_LF in C.  The record (out_H, JXS_FRAME_ROWS per target) is formed by the lane
+  // t mod G in round t / G; the Jacobian (out_a, optional, [6][6+n] per target) column 6 + j by the lane of joint j (exact
+  // zeros where j does not support L), its six base columns O_X_C M_I by the root lane.  No LDS, no allocation.
+  JXS_HD void frame_out(const V* x, const V* RF, const V* pF, const V* P, V* o) const {
+    V t[3];
+    if (A.out_repr == REPR_INERTIAL) {
+      cross(P, x + 3, t);
+#pragma unroll
+      for (int k = 0; k < 3; ++k) o[k] = x[k] + t[k], o[3 + k] = x[3 + k];
+      return;
+    }
+    cross(pF, x + 3, t);
+    V l[3] = {x[0] - t[0], x[1] - t[1], x[2] - t[2]};
+    if (A.out_repr == REPR_BODY) {
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        o[k] = RF[k] * l[0] + RF[3 + k] * l[1] + RF[6 + k] * l[2];
+        o[3 + k] = RF[k] * x[3] + RF[3 + k] * x[4] + RF[6 + k] * x[5];
+      }
+      return;
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) o[k] = l[k], o[3 + k] = x[3 + k];
+  }
+  // pose of a target: R_F = R_L R_LF, p_F = r_L + R_L p_LF (R_L, r_L of the parent lane)
+  JXS_HD void frame_pose(const V* RL, const V* rL, const V* Rlf, const V* plf, V* RF, V* pF) const {
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+#pragma unroll
+      for (int j = 0; j < 3; ++j) RF[3 * i + j] = RL[3 * i] * Rlf[j] + RL[3 * i + 1] * Rlf[3 + j] + RL[3 * i + 2] * Rlf[6 + j];
+      pF[i] = rL[i] + RL[3 * i] * plf[0] + RL[3 * i + 1] * plf[1] + RL[3 * i + 2] * plf[2];
+    }
+  }
+  JXS_HD void frames(const VI& lane, const VI& level, const VI* jump, const VI& jrow, const VM& is_joint, const VM& is_root,
+                     const V* R0, const V* R, const V* r, const V* Sl, const V* Sa, const V* vJl, const V* vJa, const V* vl,
+                     const V* va, const V* pB, const V* doff, const V* vBc, const V* om) const {
+    const V zero = V(T(0));
+    V vf[6], al[3], aa[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      vf[k] = P.floating ? vl[k] : vl[k] + vBc[k];
+      vf[3 + k] = P.floating ? va[k] : va[k] + om[k];
+    }
+    {
+      V t0[3], t1[3], ca[3], a0[3];
+      cross(vf + 3, vJl, t0);
+      cross(vf, vJa, t1);
+      cross(vf + 3, vJa, ca);
+      cross(vBc, om, a0);  // Mixed input: pdot_B x w_B
+      const bool mixed_in = A.in_repr == REPR_MIXED;
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        al[k] = vsel(is_root, mixed_in ? a0[k] : zero, vsel(is_joint, t0[k] + t1[k], zero));
+        aa[k] = vsel(is_root, zero, vsel(is_joint, ca[k], zero));
+      }
+    }
+    prefix6(jump, al, aa);
+    V Pw[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) Pw[k] = pB[k] + doff[k];
+    const int nt = A.n_tgt;
+    // ---- records: target t = round * G + lane
+    if (A.out_H != nullptr) {
+      const int rows = nt * kFrameRows;
+      for (int t0 = 0; t0 < nt; t0 += G) {
+        const VI t = lane + t0;
+        const VM ok = t < nt;
+        const VI tb = vsel(ok, t, lane * 0) * kTgtStride;
+        const VI pl = L::to_int(ln.tgather(A.tgt, tb + TG_LANE));
+        V Rlf[9], plf[3], RL[9], rL[3], v[6], a[6];
+#pragma unroll
+        for (int e = 0; e < 9; ++e) Rlf[e] = ln.tgather(A.tgt, tb + (TG_R + e));
+#pragma unroll
+        for (int e = 0; e < 3; ++e) plf[e] = ln.tgather(A.tgt, tb + (TG_P + e));
+#pragma unroll
+        for (int e = 0; e < 9; ++e) RL[e] = ln.shfl(R[e], pl);
+#pragma unroll
+        for (int e = 0; e < 3; ++e) {
+          rL[e] = ln.shfl(r[e], pl);
+          v[e] = ln.shfl(vf[e], pl), v[3 + e] = ln.shfl(vf[3 + e], pl);
+          a[e] = ln.shfl(al[e], pl), a[3 + e] = ln.shfl(aa[e], pl);
+        }
+        ln.fence();
+        V RF[9], pF[3], ov[6], oa[6];
+        frame_pose(RL, rL, Rlf, plf, RF, pF);
+        frame_out(v, RF, pF, Pw, ov);
+        frame_out(a, RF, pF, Pw, oa);
+        if (A.out_repr == REPR_MIXED) {  // + w_F x pdot_F (pdot_F = the mixed linear velocity)
+          V t2[3];
+          cross(v + 3, ov, t2);
+#pragma unroll
+          for (int k = 0; k < 3; ++k) oa[k] = oa[k] + t2[k];
+        }
+        const VI row = t * kFrameRows;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+#pragma unroll
+          for (int j = 0; j < 3; ++j) ln.gstore(A.out_H, row + (FR_POSE + 4 * i + j), RF[3 * i + j], ok, rows);
+          ln.gstore(A.out_H, row + (FR_POSE + 4 * i + 3), pF[i] + Pw[i], ok, rows);
+        }
+#pragma unroll
+        for (int k = 0; k < 6; ++k) {
+          ln.gstore(A.out_H, row + (FR_VEL + k), ov[k], ok, rows);
+          ln.gstore(A.out_H, row + (FR_BIAS + k), oa[k], ok, rows);
+        }
+      }
+    }
+    if (A.out_a == nullptr) return;
+    // ---- Jacobians: one target per iteration, every lane
+    const int nv = 6 + P.n, rows = nt * 6 * nv;
+    const VI zl = lane * 0;
+    const V S6[6] = {Sl[0], Sl[1], Sl[2], Sa[0], Sa[1], Sa[2]};
+    for (int t = 0; t < nt; ++t) {
+      const int tb = t * kTgtStride;
+      const VI pl = L::to_int(ln.tgather(A.tgt, zl + (tb + TG_LANE)));
+      V Rlf[9], plf[3], RL[9], rL[3];
+#pragma unroll
+      for (int e = 0; e < 9; ++e) Rlf[e] = ln.tgather(A.tgt, zl + (tb + TG_R + e));
+#pragma unroll
+      for (int e = 0; e < 3; ++e) plf[e] = ln.tgather(A.tgt, zl + (tb + TG_P + e));
+#pragma unroll
+      for (int e = 0; e < 9; ++e) RL[e] = ln.shfl(R[e], pl);
+#pragma unroll
+      for (int e = 0; e < 3; ++e) rL[e] = ln.shfl(r[e], pl);
+      // does this lane's joint support L?  The ancestor of L at this lane's depth, by pointer jumping, is this lane
+      const VI dist = ln.shfl(level, pl) - level;
+      VI node = pl;
+#pragma unroll
+      for (int k = 0; k < kMaxRounds; ++k) {
+        if (k < P.n_rounds) {
+          const VI up = ln.shfl(jump[k], node);
+          node = vsel(((dist >> k) & 1) == 1, up, node);
+        }
+      }
+      ln.fence();
+      const VM sup = is_joint && (dist >= 0) && (node == lane);
+      V RF[9], pF[3], S[6], o[6];
+      frame_pose(RL, rL, Rlf, plf, RF, pF);
+#pragma unroll
+      for (int k = 0; k < 6; ++k) S[k] = vsel(sup, S6[k], zero);
+      frame_out(S, RF, pF, Pw, o);
+      const VI col = vsel(is_joint, jrow + 6, zl) + t * 6 * nv;
+#pragma unroll
+      for (int i = 0; i < 6; ++i) ln.gstore(A.out_a, col + i * nv, o[i], is_joint, rows);
+      // base columns: O_X_C M_I, M_I = the C-frame base velocity per unit of input base velocity
+#pragma unroll
+      for (int c = 0; c < 6; ++c) {
+        V m[6];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) m[k] = zero;
+        if (A.in_repr == REPR_BODY) {
+#pragma unroll
+          for (int k = 0; k < 3; ++k) m[(c < 3 ? 0 : 3) + k] = R0[3 * k + (c % 3)];
+        } else {
+          m[c] = V(T(1));
+          if (A.in_repr == REPR_INERTIAL && c >= 3) {  // lin = e x p_B
+            V e[3] = {zero, zero, zero}, t2[3];
+            e[c - 3] = V(T(1));
+            cross(e, pB, t2);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) m[k] = t2[k];
+          }
+        }
+        frame_out(m, RF, pF, Pw, o);
+#pragma unroll
+        for (int i = 0; i < 6; ++i) ln.gstore(A.out_a, zl + (t * 6 * nv + i * nv + c), o[i], is_root, rows);
       }
     }
   }

@@ -31,6 +31,8 @@ struct KTail {
   int* faults;
   int flags;
   T fparam;
+  const T* tgt;  // MODE_FRAMES: target table, count and the two representations (appended: the fields above keep their offsets)
+  int n_tgt, in_repr, out_repr;
 };
 
 // OCC2 (rigid contact modes only): compiled for two waves per SIMD (at most 256 registers; a few values go
@@ -70,6 +72,7 @@ __global__ __launch_bounds__(64, VARIANT == KV_OCC2 ? 2 : JXS_MIN_WAVES) void jx
   A.hf = reinterpret_cast<const T*>(pre_mblk + P.hf_off);
   A.in_a = tail.in_a, A.out_a = tail.out_a, A.out_H = tail.out_H, A.out_V = tail.out_V, A.out_tau = tail.out_tau;
   A.id_zero_vel = tail.id_zero_vel, A.dbg = tail.dbg, A.faults = tail.faults, A.flags = tail.flags, A.fparam = tail.fparam;
+  if constexpr (MODE == jxs::MODE_FRAMES) A.tgt = tail.tgt, A.n_tgt = tail.n_tgt, A.in_repr = tail.in_repr, A.out_repr = tail.out_repr;
   if constexpr (VARIANT == KV_OCC2) A.flags |= 1;  // two waves per SIMD: 256 registers, no room for MFMA accumulator tiles
   // the state-block rows of SURVEY section 8(a) row D, derived from the preloaded joint count instead of loaded
   P.n_rows = pre_n_rows, P.n = pre_n;
@@ -167,7 +170,7 @@ hipError_t launch_one(const jxs::KParams<T>& P, const unsigned char* mblk, const
   if (rows) lds_bytes = JXS_EXP_LDS_BYTES;
 #endif
   const KTail<T> tail{A.in_a, A.out_a, A.out_H, A.out_V, A.out_tau, A.id_zero_vel, A.dbg, A.faults,
-                      A.flags | ((A.knobs & jxs::KNOB_NO_MFMA) ? 1 : 0), A.fparam};  // KNOB_NO_MFMA: A/B of the vector path of the contact solvers' Cholesky
+                      A.flags | ((A.knobs & jxs::KNOB_NO_MFMA) ? 1 : 0), A.fparam, A.tgt, A.n_tgt, A.in_repr, A.out_repr};  // KNOB_NO_MFMA: A/B of the vector path of the contact solvers' Cholesky
   if (MODE == jxs::MODE_STEP_RIGID || MODE == jxs::MODE_STEP_RK4_RIGID || MODE == jxs::MODE_DYN_RIGID) {
     lds_bytes = sizeof(T) * (size_t)envs_per_wave * jxs::rigid_lds_words_per_env(P.n_cp, P.rigid, P.ct_tree, P.n_chunks, G);
     if (lds_bytes > 64 * 1024) {  // beyond the default dynamic-LDS window (gfx950 has 160 KiB per CU)

@@ -241,9 +241,14 @@ enum Mode : int {
   // centroidal momentum, CoM and energies (api/com.py, api/model.py:1988-2175, 2397-2453): one leaves-to-root sweep of the
   // composite inertia, the subtree momentum and the subtree kinetic energy; a record per environment (KArgs::out_H,
   // include/jaxsim_amd.h JXS_CENTROIDAL_*) and, on request, the centroidal momentum matrix A_G in G[W] (KArgs::out_a)
-  MODE_CENTROIDAL = 14
+  MODE_CENTROIDAL = 14,
+  // poses, velocities, bias accelerations (J̇ν) and, on request, Jacobians of a list of frames rigidly attached to links
+  // (api/link.py, api/frame.py; api/model.py:2179-2395 link_bias_accelerations): one ancestor prefix sum of c_i = v_i x vJ_i,
+  // then a record of JXS_FRAME_ROWS rows per target (KArgs::out_H, include/jaxsim_amd.h JXS_FRAME_*) and the [6][6+n]
+  // Jacobian of every target (KArgs::out_a).  The target table (KArgs::tgt) and the representations are launch arguments.
+  MODE_FRAMES = 15
 };
-constexpr int kNumModes = 15;
+constexpr int kNumModes = 16;
 // MODE_CENTROIDAL: rows of the per-environment record (include/jaxsim_amd.h JXS_CENTROIDAL_*, checked there by jxs_api.hip)
 enum CentroidalRow : int {
   CR_COM = 0,         // 3: W_p_CoM
@@ -255,6 +260,12 @@ enum CentroidalRow : int {
   CR_MASS = 23,       // 1: total mass
   kCentRows = 24
 };
+
+// MODE_FRAMES: rows of the per-target record (include/jaxsim_amd.h JXS_FRAME_*, checked there by jxs_api.hip) and the
+// target table: kTgtStride values per target = parent LANE (exact small integer), parent link, L_H_F as R (row-major) and p
+constexpr int FR_POSE = 0, FR_VEL = 12, FR_BIAS = 18, kFrameRows = 24;
+constexpr int kTgtStride = 16, TG_LANE = 0, TG_LINK = 1, TG_R = 2, TG_P = 11;
+constexpr int kMaxFrameTargets = 4096;
 
 enum ForceRepr : int { REPR_INERTIAL = 0, REPR_BODY = 1, REPR_MIXED = 2 };  // api/common.py:39-47
 
@@ -388,6 +399,10 @@ struct KArgs {
   int has_lds;         // the launch has the per-environment LDS area of the row layout (known when the wave starts: a
                        // compile-time constant in the specialised / common-feature kernels): the thirteen
                        // environment-uniform rows of the state are fetched by ONE load instruction and spread through it
+  // MODE_FRAMES (appended: the fields above keep their offsets)
+  const T* tgt;        // [n_tgt][kTgtStride] target table (jxs_frames_create), device memory
+  int n_tgt;           // number of targets (1 .. kMaxFrameTargets)
+  int in_repr, out_repr;  // ForceRepr of the generalized velocity (input) and of the outputs
 };
 
 // ---- device model block: ONE allocation per model that the kernels address from a single pointer -------

@@ -67,6 +67,7 @@ class JaxSimModelData:
         self._host = None  # lazily downloaded dict of [N,...] arrays
         self._kin = None  # lazily computed (link_transforms, link_velocities)
         self._cent = None  # lazily computed centroidal record and momentum matrix (api/com.py)
+        self._frames = None  # lazily computed frame records per (targets, representations) (api/frame.py)
 
     # -- construction -----------------------------------------------------------------------
     @staticmethod
@@ -188,6 +189,7 @@ class JaxSimModelData:
         self._host = None
         self._kin = None
         self._cent = None
+        self._frames = None
 
     def _fields(self) -> dict:
         if self._host is None:

@@ -191,8 +191,8 @@ def _compile_locked(text: str, fields: dict, assign: str, out: pathlib.Path) -> 
 
 
 # forward dynamics, inverse dynamics, cached kinematics, mass matrix, Jacobians, mass-matrix inverse, gravity torques,
-# centroidal quantities (js.com): on request
-QUERY_MODES = (1, 2, 3, 8, 9, 10, 11, 14)
+# centroidal quantities (js.com), frames (js.link / js.frame): on request
+QUERY_MODES = (1, 2, 3, 8, 9, 10, 11, 14, 15)
 
 
 def attach(dm, model, mode: int | None = None, *, build: bool = False, require: bool = False) -> bool:
@@ -242,6 +242,7 @@ def attach(dm, model, mode: int | None = None, *, build: bool = False, require: 
 
 MODE_GRAV = 11
 MODE_CENTROIDAL = 14
+MODE_FRAMES = 15
 
 
 def ensure_mode(dm, model, mode: int) -> bool:

@@ -14,6 +14,7 @@ import argparse
 import ctypes as C
 import os
 import sys
+import time
 
 import numpy as np
 
@@ -62,6 +63,27 @@ for dtype in (np.float32, np.float64):
     acc, frc, tau, M, Mi, J, HT, HV = buf(nv), buf(nv), buf(n), buf(nv * nv), buf(nv * nv), buf(2 * 6 * nv), buf(nL * 12), buf(nL * 6)
     scratch = buf(rows_state)
     CR, AG = buf(24), buf(6 * nv)  # centroidal record (JXS_CENTROIDAL_ROWS) and momentum matrix
+    # frame records (JXS_FRAME_ROWS per target): all links; four model-frame-like targets (rotated, on four links)
+    from jaxsim_amd.api import frame as jf
+    from jaxsim_amd.api import model as jsm
+
+    FR_all, FJ_all = buf(nL * 24), buf(nL * 6 * nv)
+    H4 = np.broadcast_to(np.eye(4), (4, 4, 4)).copy()
+    for k in range(4):  # rotated about z by k * 0.4 rad, offset by a few centimetres
+        c, sn = np.cos(0.4 * k), np.sin(0.4 * k)
+        H4[k, :2, :2] = [[c, -sn], [sn, c]]
+        H4[k, :3, 3] = [0.02 * k, -0.01, 0.03]
+    T_all = jf.Targets(dm, np.arange(nL), np.broadcast_to(np.eye(4), (nL, 4, 4)))
+    T4 = jf.Targets(dm, np.array([nL - 1, nL - 2, nL // 2, 1]), H4)
+    FR4, FJ4 = buf(4 * 24), buf(4 * 6 * nv)
+
+    def host_path():  # what the record replaces: MODE_KIN + MODE_JAC, downloaded, masked and re-expressed per link
+        data._invalidate_caches()
+        jsm.generalized_free_floating_jacobian(model, data)
+        jsm.generalized_free_floating_jacobian_derivative(model, data)
+        data._link_transforms
+        stream.synchronize()
+        return 0
     cases = [
         ("forward_dynamics_aba (MODE_FD)", lambda: lib.jxs_forward_dynamics_aba(dm.handle, sp, None, None, 2, acc, N, stream.handle), rows_state + nv),
         ("free_floating_bias_forces (MODE_ID, zero acc.)", lambda: lib.jxs_inverse_dynamics(dm.handle, sp, None, None, 2, frc, N, stream.handle), rows_state + nv),
@@ -76,8 +98,24 @@ for dtype in (np.float32, np.float64):
         ("CRBA + kinematics (what MODE_CENTROIDAL replaces)",
          lambda: lib.jxs_mass_matrix(dm.handle, sp, M, N, stream.handle) or lib.jxs_refresh_kinematics(dm.handle, sp, HT, HV, N, stream.handle),
          2 * rows_state + nv * nv + nL * 18),
+        ("frames: all links, record (MODE_FRAMES)", lambda: lib.jxs_frame_kinematics(dm.handle, T_all.handle, sp, 2, 2, FR_all, None, N, stream.handle), rows_state + nL * 24),
+        ("frames: all links, record + J (MODE_FRAMES)", lambda: lib.jxs_frame_kinematics(dm.handle, T_all.handle, sp, 2, 2, FR_all, FJ_all, N, stream.handle), rows_state + nL * (24 + 6 * nv)),
+        ("frames: 4 frames, record + J (MODE_FRAMES)", lambda: lib.jxs_frame_kinematics(dm.handle, T4.handle, sp, 2, 2, FR4, FJ4, N, stream.handle), rows_state + 4 * (24 + 6 * nv)),
+        ("MODE_KIN + MODE_JAC (what MODE_FRAMES replaces)",
+         lambda: lib.jxs_refresh_kinematics(dm.handle, sp, HT, HV, N, stream.handle) or lib.jxs_jacobian_full(dm.handle, sp, J, HT, N, stream.handle),
+         2 * rows_state + nL * 18 + 2 * 6 * nv + nL * 12),
         ("step, out of place (MODE_STEP)", lambda: lib.jxs_step(dm.handle, sp, scratch, None, None, 2, N, stream.handle), 2 * rows_state),
     ]
+    # the host path MODE_FRAMES replaces: MODE_KIN + MODE_JAC, downloaded, masked and re-expressed per link on the host
+    # (js.model.generalized_free_floating_jacobian / _derivative), wall clock with a device sync, a few repetitions
+    host_path()
+    t_host = []
+    for _ in range(5):
+        t0 = time.perf_counter()
+        host_path()
+        t_host.append((time.perf_counter() - t0) * 1e6)
+    print(f"  {'host path MODE_FRAMES replaces (KIN+JAC+NumPy)':44s} {np.dtype(dtype).name[-2:]:>5s} {float(np.median(t_host)):10.2f} {N / float(np.median(t_host)):9.1f}", flush=True)
+
     for name, call, rows_moved in cases:
         for _ in range(20):
             _lib.check(call(), name)
@@ -94,7 +132,7 @@ for dtype in (np.float32, np.float64):
         us = float(np.median(best))
         kb = rows_moved * sz / 1e3
         gbs = rows_moved * sz * N / (us * 1e-6) / 1e9
-        print(f"  {name:44s} {np.dtype(dtype).name[-2:]:>5s} {us:10.2f} {N / us:9.1f} {kb:11.2f} {gbs:8.1f} {100 * gbs / 8000:6.2f}")
+        print(f"  {name:44s} {np.dtype(dtype).name[-2:]:>5s} {us:10.2f} {N / us:9.1f} {kb:11.2f} {gbs:8.1f} {100 * gbs / 8000:6.2f}", flush=True)
 
 # [round 6] the reference's three contact-model benchmarks (tests/test_benchmark.py:103-139): js.ode.system_dynamics on the humanoid
 # with SoftContacts / RigidContacts / RelaxedRigidContacts and estimate_good_contact_parameters -- ONE launch each here
