@@ -349,6 +349,16 @@ int jxs_mass_matrix_inverse(jxs_model* model, const void* state, void* out_Minv,
 #define JXS_CENTROIDAL_ROWS 24
 int jxs_centroidal(jxs_model* model, const void* state, void* out_record, void* out_cmm, int N, void* stream);
 
+/* free_floating_coriolis_matrix (src/jaxsim/api/model.py:1634-1745): C(q, nu) with C nu = h - g and Mdot - 2C
+ * skew-symmetric, equal entry by entry to the reference's sum over the links, one launch (a leaves-to-root sweep of the
+ * composite inertia and of sum (v_L x*) M_L).  out_C = [(6+n)*(6+n)][N], row-major (the layout of
+ * jxs_mass_matrix), in MIXED velocity representation; out_M = NULL or the Mixed mass matrix of the same launch, equal to
+ * jxs_mass_matrix's.  As in the reference the generalized velocity of a fixed-base model includes its stored base
+ * velocity.  Body / Inertial are T^T (M Tdot + C T) with T = diag(X, 1), v_mixed = X v_repr, applied by the caller.
+ * Refused with JXS_EINVAL: a null out_C, model or state, N <= 0.  Both outputs are zeroed with hipMemsetAsync, nothing
+ * is allocated and the host does not wait (legal inside a stream capture).                               */
+int jxs_coriolis(jxs_model* model, const void* state, void* out_C, void* out_M, int N, void* stream);
+
 /* Frames: poses, velocities, bias accelerations and Jacobians of frames rigidly attached to links, one launch
  * (jaxsim.api.link: transform, velocity, jacobian, bias_acceleration; jaxsim.api.frame: transform, velocity, jacobian;
  * jaxsim.api.model.link_bias_accelerations, src/jaxsim/api/model.py:2179-2395).  A target is (parent link L, L_H_F); a

@@ -243,6 +243,7 @@ def _declare(lib):
         "jxs_refresh_kinematics": [vp, vp, vp, vp, C.c_int, vp],
         "jxs_mass_matrix": [vp, vp, vp, C.c_int, vp],
         "jxs_centroidal": [vp, vp, vp, vp, C.c_int, vp],
+        "jxs_coriolis": [vp, vp, vp, vp, C.c_int, vp],
         "jxs_frames_create": [vp, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(vp)],
         "jxs_frames_destroy": [vp],
         "jxs_frame_kinematics": [vp, vp, vp, C.c_int, C.c_int, vp, vp, C.c_int, vp],

@@ -812,3 +812,84 @@ def forward_kinematics(model: JaxSimModel, data: JaxSimModelData) -> np.ndarray:
     """``forward_kinematics`` (``src/jaxsim/api/model.py:474-493``): ``W_H_L`` of all links, [nL, 4, 4] / [N, nL, 4, 4],
     from the cached kinematics (the kinematics kernel, ``MODE_KIN``)."""
     return data._link_transforms
+
+
+# ---- Coriolis matrix (src/jaxsim/api/model.py:1634-1745): one launch of the Coriolis kernel (jxs_coriolis,
+#      MODE_CORIOLIS), which returns C and M in Mixed representation; the other representations on the host
+
+
+def coriolis_matrix_device(model: JaxSimModel, data: JaxSimModelData, *, out: DeviceArray | None = None,
+                           out_mass_matrix: DeviceArray | None = None, mass_matrix: bool = False):  # fmt: skip
+    """Extension for device-resident loops (like ``js.com.centroidal_quantities``): the free-floating Coriolis matrix in
+    MIXED representation as a ``DeviceArray`` ``[(6+n)^2][N]`` (row-major, the layout of ``jxs_mass_matrix``) -- and with
+    ``mass_matrix=True`` or ``out_mass_matrix`` the pair ``(C, M)``, the Mixed mass matrix of the same launch.  One
+    launch, no host round trip; ``out`` / ``out_mass_matrix`` are reused when given."""
+    from .. import specialize
+
+    dm = runtime.device_model(model, data.dtype)
+    specialize.ensure_mode(dm, model, specialize.MODE_CORIOLIS)  # (first call: cached object, or built when hipcc is there)
+    N, nv = data.batch_size, 6 + model.dofs()
+    tile = data._state.tile
+    want = (nv * nv, N, np.dtype(data.dtype), tile)
+
+    def buffer(b):
+        b = b if b is not None else DeviceArray(nv * nv, N, data.dtype, tile=tile)
+        if (b.rows, b.cols, b.dtype, b.tile) != want:
+            raise ValueError(((b.rows, b.cols, b.dtype, b.tile), want))
+        return b
+
+    out = buffer(out)
+    with_M = mass_matrix or out_mass_matrix is not None
+    out_mass_matrix = buffer(out_mass_matrix) if with_M else None
+    _lib.check(
+        _lib.load().jxs_coriolis(dm.handle, C.c_void_p(data._state.ptr), C.c_void_p(out.ptr), _ptr(out_mass_matrix), N,
+                                 runtime._sp()),
+        "jxs_coriolis",
+    )  # fmt: skip
+    return (out, out_mass_matrix) if with_M else out
+
+
+def _coriolis_mixed_to(rep, W_H_B: np.ndarray, BW_v_WB: np.ndarray, C_mixed: np.ndarray, M_mixed: np.ndarray) -> np.ndarray:
+    """``C`` in representation ``rep`` from the Mixed ``C`` and ``M`` of the kernel: ``T^T (M Tdot + C T)`` with
+    ``T = diag(X, 1)``, ``X`` = ``_mixed_to_repr_block`` (``v_mixed = X v_rep``) and its time derivative for the base
+    velocity ``BW_v_WB`` (Mixed, [N, 6]): Body ``Xdot = diag(S(w) R, S(w) R)``, Inertial ``Xdot[0:3, 3:6] = -S(pdot)``."""
+    from .com import _skew
+
+    if rep == VelRepr.Mixed:
+        return C_mixed
+    N = C_mixed.shape[0]
+    X, Xd = np.zeros((N, 6, 6)), np.zeros((N, 6, 6))
+    if rep == VelRepr.Body:
+        R = W_H_B[:, :3, :3]
+        Rd = _skew(BW_v_WB[:, 3:]) @ R
+        X[:, :3, :3] = X[:, 3:, 3:] = R
+        Xd[:, :3, :3] = Xd[:, 3:, 3:] = Rd
+    else:
+        X[:, :3, :3] = X[:, 3:, 3:] = np.eye(3)
+        X[:, :3, 3:] = -_skew(W_H_B[:, :3, 3])
+        Xd[:, :3, 3:] = -_skew(BW_v_WB[:, :3])
+    # T^T (M Tdot + C T): Tdot touches only columns 0:6, T only the base rows / columns
+    out = C_mixed.copy()
+    out[:, :, :6] = C_mixed[:, :, :6] @ X + M_mixed[:, :, :6] @ Xd
+    out[:, :6, :] = np.transpose(X, (0, 2, 1)) @ out[:, :6, :]
+    return out
+
+
+def free_floating_coriolis_matrix(model: JaxSimModel, data: JaxSimModelData):
+    """``free_floating_coriolis_matrix`` (``src/jaxsim/api/model.py:1634-1745``): ``C(q, nu)`` in the data's velocity
+    representation, [6+n, 6+n] / [N, 6+n, 6+n].  ONE launch of the Coriolis kernel (``jxs_coriolis``) returns C and M in
+    Mixed representation (a tree recursion over the composite inertia, not the reference's sum over dense link
+    Jacobians); Body / Inertial are ``T^T (M Tdot + C T)`` on the host, as in the reference.  Like the reference, a
+    fixed-base model keeps the stored base velocity in nu and the base block of C."""
+    N, nv = data.batch_size, 6 + model.dofs()
+    rep = data.velocity_representation
+    if rep == VelRepr.Mixed:
+        Cd = coriolis_matrix_device(model, data)
+        Cm = Cd.to_host().T.astype(np.float64).reshape(N, nv, nv)
+        return data._out(Cm.astype(data.dtype))
+    Cd, Md = coriolis_matrix_device(model, data, mass_matrix=True)
+    Cm = Cd.to_host().T.astype(np.float64).reshape(N, nv, nv)
+    Mm = Md.to_host().T.astype(np.float64).reshape(N, nv, nv)
+    v = np.asarray(data._base_velocity_batched(VelRepr.Mixed), np.float64)
+    out = _coriolis_mixed_to(rep, data._base_transform_batched(), v, Cm, Mm)
+    return data._out(out.astype(data.dtype))

@@ -101,6 +101,7 @@ hipError_t launch_mode(int mode, int G, const jxs::KParams<T>& P, const unsigned
     case jxs::MODE_DYN_RIGID: return launch_g<T, jxs::MODE_DYN_RIGID>(G, P, mblk, A, s);
     case jxs::MODE_CENTROIDAL: return launch_g<T, jxs::MODE_CENTROIDAL>(G, P, mblk, A, s);
     case jxs::MODE_FRAMES: return launch_g<T, jxs::MODE_FRAMES>(G, P, mblk, A, s);
+    case jxs::MODE_CORIOLIS: return launch_g<T, jxs::MODE_CORIOLIS>(G, P, mblk, A, s);
     default: return launch_g<T, jxs::MODE_KIN>(G, P, mblk, A, s);
   }
 }
@@ -113,8 +114,8 @@ struct ModelT {
   unsigned char* mblk = nullptr;
   // model-specialised kernels (jxs_model_attach_specialized): launch entry per mode, null = generic kernel
   using SpecLaunch = int (*)(const void*, const unsigned char*, const void*, void*);
-  SpecLaunch spec_launch[16] = {};
-  void* spec_handle[16] = {};
+  SpecLaunch spec_launch[jxs::kNumModes] = {};
+  void* spec_handle[jxs::kNumModes] = {};
   int* faults = nullptr;  // [2] discarded contact-force / impact solves since the last reset (rigid contact models)
   // jxs_rollout_controlled, one launch per step: the torques of the current step, [n][N] -- one block per stream
   std::mutex scratch_mu;
@@ -293,7 +294,7 @@ int run_typed(jxs_model* model, int mode, const void* state_in, void* state_out,
                                row_bytes * n * seq_steps, row_bytes * n, (size_t)((N + tile - 1) / tile), hipMemcpyDeviceToDevice, s));
       a.tau = static_cast<const T*>(scratch);
     }
-    hipError_t e = (mode >= 0 && mode < 16 && mt->spec_launch[mode] != nullptr)
+    hipError_t e = (mode >= 0 && mode < jxs::kNumModes && mt->spec_launch[mode] != nullptr)
                        ? static_cast<hipError_t>(mt->spec_launch[mode](&mt->pk.P, mt->mblk, &a, s))
                        : launch_mode<T>(mode, mt->pk.G, mt->pk.P, mt->mblk, a, s);
     if (e != hipSuccess) return hip_fail(e, "kernel launch");
@@ -562,14 +563,14 @@ int jxs_kernel_spec(const jxs_model_desc* desc, int mode, char* buf, int capacit
 
 int jxs_model_attach_specialized(jxs_model* model, int mode, const char* path) {
   if (model == nullptr || path == nullptr) return fail(JXS_EINVAL, "null argument");
-  if (mode < 0 || mode >= 16) return fail(JXS_EINVAL, "invalid mode");
+  if (mode < 0 || mode >= jxs::kNumModes) return fail(JXS_EINVAL, "invalid mode");
   return model->dtype == JXS_F64 ? attach_typed<double>(model, model->f64.get(), mode, path)
                                  : attach_typed<float>(model, model->f32.get(), mode, path);
 }
 int jxs_model_specialized_modes(const jxs_model* model, unsigned* mask) {
   if (model == nullptr || mask == nullptr) return fail(JXS_EINVAL, "null argument");
   unsigned m = 0;
-  for (int k = 0; k < 16; ++k) {
+  for (int k = 0; k < jxs::kNumModes; ++k) {
     const bool on = model->dtype == JXS_F64 ? model->f64->spec_launch[k] != nullptr : model->f32->spec_launch[k] != nullptr;
     if (on) m |= 1u << k;
   }
@@ -915,6 +916,22 @@ int jxs_centroidal(jxs_model* model, const void* state, void* out_record, void* 
   // does not wait -- legal inside a stream capture
   if (out_record == nullptr) return fail(JXS_EINVAL, "null out_record");
   return run_any(model, jxs::MODE_CENTROIDAL, state, nullptr, nullptr, nullptr, 0, nullptr, out_cmm, out_record, nullptr, N, 1, stream);
+}
+int jxs_coriolis(jxs_model* model, const void* state, void* out_C, void* out_M, int N, void* stream) {
+  // [MODE_CORIOLIS] the kernel writes the structurally non-zero entries of C (and of M): both are zeroed first with
+  // hipMemsetAsync, like jxs_mass_matrix -- nothing is allocated and the host does not wait (legal inside a stream capture)
+  if (out_C == nullptr) return fail(JXS_EINVAL, "null out_C");
+  if (model == nullptr) return fail(JXS_EINVAL, "null model");
+  if (state == nullptr) return fail(JXS_EINVAL, "null state");
+  if (N <= 0) return fail(JXS_EINVAL, "N must be positive");
+  jxs_layout lay;
+  jxs_model_layout(model, &lay);
+  const size_t nv = 6 + (size_t)lay.n_joints;
+  const size_t bytes = (size_t)((N + lay.tile - 1) / lay.tile) * lay.tile * nv * nv * (model->dtype == JXS_F64 ? 8 : 4);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  JXS_HIP(hipMemsetAsync(out_C, 0, bytes, s));
+  if (out_M != nullptr) JXS_HIP(hipMemsetAsync(out_M, 0, bytes, s));
+  return run_any(model, jxs::MODE_CORIOLIS, state, nullptr, nullptr, nullptr, 0, nullptr, out_C, out_M, nullptr, N, 1, stream);
 }
 int jxs_frames_create(jxs_model* model, int n, const int32_t* parent_link, const double* L_H_F, jxs_frames** out) {
   if (out == nullptr) return fail(JXS_EINVAL, "null out");

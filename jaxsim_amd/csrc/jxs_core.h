@@ -777,6 +777,10 @@ struct Core {
       centroidal(lane, level, child, jrow, is_joint, is_root, MA, S6, vl, va, pB, doff, vBc, om);
       return;
     }
+    if (MODE == MODE_CORIOLIS) {
+      coriolis(lane, level, child, jrow, is_joint, is_root, MA, S6, vl, va, vBc, om);
+      return;
+    }
 
     V sdd = V(T(0));
     V acl[3], aca[3];  // base spatial acceleration in C incl. gravity (valid in every lane)
@@ -2923,6 +2927,177 @@ struct Core {
       for (int i = 0; i < 3; ++i) {
         ln.gstore(A.out_a, zl + (i * nv + j), ml[i], is_root, rows);
         ln.gstore(A.out_a, zl + ((3 + i) * nv + j), Ic[sidx(3 + i, j)] - t[i], is_root, rows);
+      }
+    }
+  }
+
+  // ==========================================================================================
+  // Free-floating Coriolis matrix (api/model.py:1634-1745) in MIXED representation.  The reference sums
+  //   C_B = sum_L J_L^T ((v_L x*) M_L + M_L (v_L x)) J_L + J_L^T M_L Jdot_L
+  // in body-fixed form and moves it with C = T^T (M_B Tdot + C_B T).  The sum is covariant: in frame C, held fixed at
+  // the instant, it is  C_fix = sum_L J_L^T ((v_L x*) M_L J_L + M_L Jdot_L),  the base columns of J_L are the identity
+  // (zero derivative) and column j of Jdot_L is Sdot_j = v_j x S_j.  With the composite inertia I_k and
+  // B_k = sum_{L in subtree(k)} (v_L x*) M_L of one leaves-to-root sweep (the child gathers of crba()):
+  //   F_k = B_k S_k + I_k Sdot_k,  G_k = B_k^T S_k,  H_k = I_k S_k  (= column k of M)
+  //   C[j, k] = S_j . F_k,  C[k, j] = G_k . S_j + H_k . Sdot_j   for every ancestor-or-self joint j of k,
+  //   C[0:6, 0:6] = B_0,  C[0:6, k] = F_k,  C[k, 0:6] = G_k^T.
+  // Mixed = C_fix + M Tdot (T = 1 at the instant; Tdot[0:3, 3:6] = S(pdot_B), the base position moving away from the
+  // origin of C): columns 3..5 of the base block gain I_0[:, 0:3] S(pdot_B), those of row k gain H_k,lin^T S(pdot_B).
+  // A fixed base (the reference drops link 0 and zeroes the blocks [0:6, 6:] and [6:, 0:6] of C_B, then applies the same
+  // congruence): the base block loses M_0 (v_0 x) as well -- the root's own B is -M_0 (v_0 x) = ((v_0 x*) M_0)^T -- the
+  // column F_k is zero and row k is -H_k^T vx([0; w_B]) = [w_B x H_k,lin ; w_B x H_k,ang].  As in the reference the
+  // generalized velocity includes the stored base velocity of a fixed base.
+  // out_a = C, [(6+n)^2][N] row-major; out_H (optional) = M of the same sweep, the entries crba() writes.  No LDS.
+  JXS_HD void coriolis(const VI& lane, const VI& level, const VI* child, const VI& jrow, const VM& is_joint,
+                       const VM& is_root, const V* M_link, const V* S6, const V* vl, const V* va, const V* vBc,
+                       const V* om) const {
+    const V zero = V(T(0));
+    V v6[6], Sd[6];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      v6[k] = P.floating ? vl[k] : vl[k] + vBc[k];
+      v6[3 + k] = P.floating ? va[k] : va[k] + om[k];
+    }
+    {  // Sdot = v x S
+      V t0[3], t1[3];
+      cross(v6 + 3, S6, t0);
+      cross(v6, S6 + 3, t1);
+      cross(v6 + 3, S6 + 3, Sd + 3);
+#pragma unroll
+      for (int k = 0; k < 3; ++k) Sd[k] = t0[k] + t1[k];
+    }
+    // X = [I (21, upper triangle) | B (36, row-major)] of this lane's link, summed over the subtree below
+    V X[57];
+#pragma unroll
+    for (int e = 0; e < 21; ++e) X[e] = M_link[e];
+    V* const B = X + 21;
+#pragma unroll
+    for (int c = 0; c < 6; ++c) {  // column c of (v x*) M = [w x m_lin ; v x m_lin + w x m_ang], m = column c of M
+      V m[6], o[6], t[3];
+#pragma unroll
+      for (int i = 0; i < 6; ++i) m[i] = M_link[sidx(i, c)];
+      cross(v6 + 3, m, o);
+      cross(v6, m, o + 3);
+      cross(v6 + 3, m + 3, t);
+#pragma unroll
+      for (int k = 0; k < 3; ++k) o[3 + k] = o[3 + k] + t[k];
+#pragma unroll
+      for (int i = 0; i < 6; ++i) B[6 * i + c] = o[i];
+    }
+    if (!P.floating) {  // the root of a fixed base: the transpose
+      V Bt[36];
+#pragma unroll
+      for (int i = 0; i < 6; ++i)
+#pragma unroll
+        for (int c = 0; c < 6; ++c) Bt[6 * i + c] = vsel(is_root, B[6 * c + i], B[6 * i + c]);
+#pragma unroll
+      for (int e = 0; e < 36; ++e) B[e] = Bt[e];
+    }
+    for (int Lv = P.max_depth; Lv >= 1; --Lv) {
+      const VM is_par = level == (Lv - 1);
+      const int nch = P.maxch(Lv);
+      if (nch >= 1) {
+        const VM ok0 = is_par && (child[0] >= 0);
+#pragma unroll
+        for (int g = 0; g < 5; ++g) {
+          V s9[9];
+#pragma unroll
+          for (int e = 0; e < 9; ++e) s9[e] = X[9 * g + e];
+          add_from_next<9>(lane, X + 9 * g, s9, ok0);
+        }
+#pragma unroll
+        for (int g = 0; g < 2; ++g) {
+          V s6[6];
+#pragma unroll
+          for (int e = 0; e < 6; ++e) s6[e] = X[45 + 6 * g + e];
+          add_from_next<6>(lane, X + 45 + 6 * g, s6, ok0);
+        }
+      }
+#pragma unroll
+      for (int k = 1; k < kMaxChildren; ++k) {
+        if (k >= P.max_children) break;  // (the widest link of the MODEL: a constant of a model-specialised kernel)
+        if (k < nch) {
+          const V okf = vsel(is_par && (child[k] >= 0), V(T(1)), zero);
+#pragma unroll
+          for (int h = 0; h < 57; h += 19) {  // three gathers of 19: fewer registers in flight
+            V g[19];
+#pragma unroll
+            for (int e = 0; e < 19; ++e) g[e] = ln.shfl(X[h + e], child[k]);
+            ln.fence();
+#pragma unroll
+            for (int e = 0; e < 19; ++e) X[h + e] = X[h + e] + okf * g[e];
+          }
+        }
+      }
+    }
+    const V* const Ic = X;
+    V F[6], Gk[6], H[6];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+      V h = Ic[sidx(i, 0)] * S6[0], f = B[6 * i] * S6[0], g = B[i] * S6[0];
+#pragma unroll
+      for (int j = 1; j < 6; ++j) h = h + Ic[sidx(i, j)] * S6[j], f = f + B[6 * i + j] * S6[j], g = g + B[6 * j + i] * S6[j];
+#pragma unroll
+      for (int j = 0; j < 6; ++j) f = f + Ic[sidx(i, j)] * Sd[j];
+      H[i] = h, F[i] = f, Gk[i] = g;
+    }
+    const int nv = 6 + P.n, rows = nv * nv;
+    const VI zl = lane * 0;
+    T* const outM = A.out_H;
+    // base block (root lane): B_0 + I_0 Tdot, columns 3..5 of row i gain I_0[i, 0:3] x pdot_B
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+      const V a[3] = {Ic[sidx(i, 0)], Ic[sidx(i, 1)], Ic[sidx(i, 2)]};
+      V t[3];
+      cross(a, vBc, t);
+#pragma unroll
+      for (int j = 0; j < 6; ++j) ln.gstore(A.out_a, zl + (i * nv + j), B[6 * i + j] + (j >= 3 ? t[j - 3] : zero), is_root, rows);
+      if (outM != nullptr) {
+#pragma unroll
+        for (int j = 0; j < 6; ++j) ln.gstore(outM, zl + (i * nv + j), Ic[sidx(i, j)], is_root, rows);
+      }
+    }
+    const VI sub = ln.lconsti(A.lti, LI_SUBTREE);
+    const VI rj = jrow + 6;
+    // one pass per link lane k: the ancestor-or-self joints j of k write C[j, k] (and, j != k, C[k, j]); the root lane
+    // writes the base column and row of k
+    for (int k = 1; k < P.nL; ++k) {
+      const VI src = zl + k;
+      V f[6], g[6], h[6];
+#pragma unroll
+      for (int e = 0; e < 6; ++e) f[e] = ln.shfl(F[e], src), g[e] = ln.shfl(Gk[e], src), h[e] = ln.shfl(H[e], src);
+      const VI ck = ln.shfl(jrow, src) + 6;  // column of joint k
+      ln.fence();
+      V cjk = S6[0] * f[0], ckj = g[0] * S6[0] + h[0] * Sd[0], mjk = S6[0] * h[0];
+#pragma unroll
+      for (int e = 1; e < 6; ++e) cjk = cjk + S6[e] * f[e], ckj = ckj + g[e] * S6[e] + h[e] * Sd[e], mjk = mjk + S6[e] * h[e];
+      const VM anc = is_joint && (lane <= src) && (src < lane + sub);
+      ln.gstore(A.out_a, rj * nv + ck, cjk, anc, rows);
+      ln.gstore(A.out_a, ck * nv + rj, ckj, anc && (lane < src), rows);
+      if (outM != nullptr) {
+        ln.gstore(outM, rj * nv + ck, mjk, anc, rows);
+        ln.gstore(outM, ck * nv + rj, mjk, anc, rows);
+      }
+      V row[6];
+      if (P.floating) {
+        V t[3];
+        cross(h, vBc, t);  // H_k,lin^T S(pdot_B) = H_k,lin x pdot_B
+#pragma unroll
+        for (int e = 0; e < 3; ++e) row[e] = g[e], row[3 + e] = g[3 + e] + t[e];
+#pragma unroll
+        for (int e = 0; e < 6; ++e) ln.gstore(A.out_a, ck + e * nv, f[e], is_root, rows);
+      } else {
+        cross(om, h, row);
+        cross(om, h + 3, row + 3);
+      }
+#pragma unroll
+      for (int e = 0; e < 6; ++e) ln.gstore(A.out_a, ck * nv + e, row[e], is_root, rows);
+      if (outM != nullptr) {
+#pragma unroll
+        for (int e = 0; e < 6; ++e) {
+          ln.gstore(outM, ck + e * nv, h[e], is_root, rows);
+          ln.gstore(outM, ck * nv + e, h[e], is_root, rows);
+        }
       }
     }
   }

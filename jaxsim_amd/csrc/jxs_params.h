@@ -246,9 +246,13 @@ enum Mode : int {
   // (api/link.py, api/frame.py; api/model.py:2179-2395 link_bias_accelerations): one ancestor prefix sum of c_i = v_i x vJ_i,
   // then a record of JXS_FRAME_ROWS rows per target (KArgs::out_H, include/jaxsim_amd.h JXS_FRAME_*) and the [6][6+n]
   // Jacobian of every target (KArgs::out_a).  The target table (KArgs::tgt) and the representations are launch arguments.
-  MODE_FRAMES = 15
+  MODE_FRAMES = 15,
+  // free-floating Coriolis matrix C(q, nu) in MIXED representation (api/model.py:1634-1745): one leaves-to-root sweep of
+  // the composite inertia and of B_k = sum (v_L x*) M_L over the subtree, then the entries of every ancestor pair
+  // (KArgs::out_a, [(6+n)^2][N]) and, on request, the mass matrix of the same launch (KArgs::out_H, jxs_mass_matrix layout)
+  MODE_CORIOLIS = 16
 };
-constexpr int kNumModes = 16;
+constexpr int kNumModes = 17;
 // MODE_CENTROIDAL: rows of the per-environment record (include/jaxsim_amd.h JXS_CENTROIDAL_*, checked there by jxs_api.hip)
 enum CentroidalRow : int {
   CR_COM = 0,         // 3: W_p_CoM

@@ -191,8 +191,8 @@ def _compile_locked(text: str, fields: dict, assign: str, out: pathlib.Path) -> 
 
 
 # forward dynamics, inverse dynamics, cached kinematics, mass matrix, Jacobians, mass-matrix inverse, gravity torques,
-# centroidal quantities (js.com), frames (js.link / js.frame): on request
-QUERY_MODES = (1, 2, 3, 8, 9, 10, 11, 14, 15)
+# centroidal quantities (js.com), frames (js.link / js.frame), Coriolis matrix: on request
+QUERY_MODES = (1, 2, 3, 8, 9, 10, 11, 14, 15, 16)
 
 
 def attach(dm, model, mode: int | None = None, *, build: bool = False, require: bool = False) -> bool:
@@ -243,6 +243,7 @@ def attach(dm, model, mode: int | None = None, *, build: bool = False, require: 
 MODE_GRAV = 11
 MODE_CENTROIDAL = 14
 MODE_FRAMES = 15
+MODE_CORIOLIS = 16
 
 
 def ensure_mode(dm, model, mode: int) -> bool:
@@ -271,7 +272,7 @@ def modes(dm) -> list[int]:
     """Modes of the device model that run a specialised kernel."""
     mask = C.c_uint()
     _lib.check(_lib.load().jxs_model_specialized_modes(dm.handle, C.byref(mask)), "jxs_model_specialized_modes")
-    return [k for k in range(16) if mask.value >> k & 1]
+    return [k for k in range(32) if mask.value >> k & 1]
 
 
 def hipcc_available() -> bool:

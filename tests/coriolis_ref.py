@@ -1,0 +1,134 @@
+"""TEST INFRASTRUCTURE for js.model.free_floating_coriolis_matrix: the reference's ``C(q, nu)`` restated in NumPy float64.
+
+``coriolis(model, d)`` follows ``src/jaxsim/api/model.py:1634-1745`` line by line for an oracle data object ``d``
+(``oracle.refstep.OracleData``), in ``d.velocity_representation``:
+
+* ``L_J_WL_B``: ``oracle.refrigid.generalized_free_floating_jacobian(model, d, Body, Body)``;
+* ``L_Jdot_WL_B``: the Body-input, Body-output branch of ``generalized_free_floating_jacobian_derivative``
+  (``model.py:1104-1214``), restated here over ``oracle.refrigid.jacobian_derivative_full_doubly_left``;
+* ``L_M_L``: the link inertias of ``oracle.refstep``; ``L_v_WL = L_J_WL_B B_nu``;
+* ``C_B = sum_L J^T ((v x*) M + M (v x)) J + J^T M Jdot``; a fixed base drops link 0 and zeroes the
+  ``[0:6, 6:]`` / ``[6:, 0:6]`` blocks;
+* Inertial / Mixed: ``C = T^T (M_B Tdot + C_B T)`` with ``M_B`` = ``oracle.refstep.free_floating_mass_matrix`` in Body.
+
+``jacobian_derivative_body_via_inertial`` moves ``oracle.refrigid.generalized_free_floating_jacobian_derivative_inertial``
+to Body input and output: an independent route to ``L_Jdot_WL_B`` for the cross-check of tests/test_coriolis_cpu.py.
+"""
+
+from __future__ import annotations
+
+import dataclasses
+
+import numpy as np
+
+from oracle import VelRepr
+from oracle import refmath as rm
+from oracle import refrigid as rr
+from oracle import refstep as rs
+
+
+def _with_rep(model, d, rep):
+    out = dataclasses.replace(d, velocity_representation=rep)
+    out._model = model
+    return out
+
+
+def jacobian_derivative_body(model, d):
+    """``generalized_free_floating_jacobian_derivative`` with Body input and Body output (model.py:1048-1228):
+    ``L_Jdot_WL_B`` [N, nL, 6, 6+n].  T = 1, Tdot = 0 (:1125-1134); ``O_X_B = L_X_B`` and
+    ``O_Xdot_B = -L_X_B vx(B_X_L L_v_WL - B_v_WB)`` (:1162-1177)."""
+    s = d.joint_positions.astype(np.float64)
+    sd = d.joint_velocities.astype(np.float64)
+    B_J_full, B_H_L = rr.jacobian_full_doubly_left(model, s)
+    B_Jd_full = rr.jacobian_derivative_full_doubly_left(model, s, sd)
+    mask = rr._support_mask(model, np.float64)[None, :, None, :]
+    B_J_WL_B = mask * B_J_full[:, None]
+    B_Jd_WL_B = mask * B_Jd_full[:, None]
+    L_X_B = rm.adjoint_from_transform(B_H_L, inverse=True)
+    B_X_L = rm.adjoint_from_transform(B_H_L)
+    B_v_WB = d.base_velocity(VelRepr.Body).astype(np.float64)
+    B_nu = np.concatenate([B_v_WB, sd], -1)
+    L_v_WL = np.einsum("nlij,nj->nli", L_X_B @ B_J_WL_B, B_nu)
+    L_Xd_B = -L_X_B @ rm.vx(np.einsum("nlij,nlj->nli", B_X_L, L_v_WL) - B_v_WB[:, None])
+    return L_Xd_B @ B_J_WL_B + L_X_B @ B_Jd_WL_B
+
+
+def jacobian_derivative_body_via_inertial(model, d):
+    """``L_Jdot_WL_B`` from the oracle's Inertial/Inertial derivative: with ``L_J_WL_B = L_X_W W_J_WL_W T``,
+    ``T = diag(W_X_B, 1)``:  ``L_Jdot = L_Xdot_W W_J T + L_X_W W_Jdot T + L_X_W W_J Tdot``,
+    ``L_Xdot_W = -vx(L_v_WL) L_X_W``, ``W_Xdot_B = W_X_B vx(B_v_WB)``."""
+    n = model.kin_dyn_parameters.number_of_joints()
+    dW = _with_rep(model, d, VelRepr.Inertial)
+    W_J = rr.generalized_free_floating_jacobian(model, dW, VelRepr.Inertial, VelRepr.Inertial)
+    W_Jd = rr.generalized_free_floating_jacobian_derivative_inertial(model, dW)
+    W_H_B = d.base_transform.astype(np.float64)
+    _, B_H_L = rr.jacobian_full_doubly_left(model, d.joint_positions.astype(np.float64))
+    W_H_L = W_H_B[:, None] @ B_H_L
+    L_X_W = rm.adjoint_from_transform(W_H_L, inverse=True)
+    W_nu = d.generalized_velocity(VelRepr.Inertial).astype(np.float64)
+    L_v_WL = np.einsum("nlij,nj->nli", L_X_W @ W_J, W_nu)
+    L_Xd_W = -rm.vx(L_v_WL) @ L_X_W
+    W_X_B = rm.adjoint_from_transform(W_H_B)
+    B_v_WB = d.base_velocity(VelRepr.Body).astype(np.float64)
+    T = rr._block_diag_T(W_X_B, n)[:, None]
+    Td = rr._block_diag_Td(W_X_B @ rm.vx(B_v_WB), n)[:, None]
+    return L_Xd_W @ W_J @ T + L_X_W @ W_Jd @ T + L_X_W @ W_J @ Td
+
+
+def coriolis_body(model, d):
+    """``C_B`` [N, 6+n, 6+n] (model.py:1658-1700)."""
+    B_nu = d.generalized_velocity(VelRepr.Body).astype(np.float64)
+    dB = _with_rep(model, d, VelRepr.Body)
+    L_J_WL_B = rr.generalized_free_floating_jacobian(model, dB, VelRepr.Body, VelRepr.Body).astype(np.float64)
+    L_Jd_WL_B = jacobian_derivative_body(model, d)
+    L_M_L = rs._link_spatial_inertia(model, np.float64)[None]
+    L_v_WL = np.einsum("nlij,nj->nli", L_J_WL_B, B_nu)
+    Jt = np.swapaxes(L_J_WL_B, -1, -2)
+    C_links = Jt @ ((rm.vx_star(L_v_WL) @ L_M_L + L_M_L @ rm.vx(L_v_WL)) @ L_J_WL_B + L_M_L @ L_Jd_WL_B)
+    if model.floating_base():
+        return C_links.sum(axis=1)
+    C_B = C_links[:, 1:].sum(axis=1)
+    C_B[:, 0:6, 6:] = 0.0
+    C_B[:, 6:, 0:6] = 0.0
+    return C_B
+
+
+def coriolis(model, d):
+    """``free_floating_coriolis_matrix`` in ``d.velocity_representation`` (model.py:1634-1745)."""
+    C_B = coriolis_body(model, d)
+    rep = d.velocity_representation
+    if rep == VelRepr.Body:
+        return C_B
+    n = model.kin_dyn_parameters.number_of_joints()
+    W_H_B = d.base_transform.astype(np.float64)
+    if rep == VelRepr.Inertial:  # :1707-1722
+        X = rm.adjoint_from_transform(W_H_B, inverse=True)
+        W_v_WB = d.base_velocity(VelRepr.Inertial).astype(np.float64)
+        Xd = -X @ rm.vx(W_v_WB)
+    else:  # Mixed, :1724-1742
+        BW_H_B = W_H_B.copy()
+        BW_H_B[:, 0:3, 3] = 0.0
+        X = rm.adjoint_from_transform(BW_H_B, inverse=True)
+        BW_v_WB = d.base_velocity(VelRepr.Mixed).astype(np.float64)
+        BW_v_W_BW = BW_v_WB.copy()
+        BW_v_W_BW[:, 3:6] = 0.0
+        Xd = -X @ rm.vx(BW_v_WB - BW_v_W_BW)
+    T = rr._block_diag_T(X, n)
+    Td = rr._block_diag_Td(Xd, n)
+    M = rs.free_floating_mass_matrix(model, _with_rep(model, d, VelRepr.Body)).astype(np.float64)
+    return np.swapaxes(T, -1, -2) @ (M @ Td + C_B @ T)
+
+
+def advance(model, d, t):
+    """The state moved by ``t`` along qdot: position by pdot_B, the quaternion by the body angular velocity, joints by sdot."""
+    pd = d.base_velocity(VelRepr.Mixed)[:, :3]
+    wB = d.base_velocity(VelRepr.Body)[:, 3:]
+    nrm = np.linalg.norm(wB, axis=-1, keepdims=True)
+    ax = wB / np.where(nrm == 0, 1.0, nrm)
+    dq = np.concatenate([np.cos(nrm * t / 2), np.sin(nrm * t / 2) * ax], -1)
+    q = d.base_quaternion
+    w1, v1, w2, v2 = q[:, :1], q[:, 1:], dq[:, :1], dq[:, 1:]
+    qn = np.concatenate([w1 * w2 - np.sum(v1 * v2, -1, keepdims=True), w1 * v2 + w2 * v1 + np.cross(v1, v2)], -1)
+    out = dataclasses.replace(d, base_position=d.base_position + t * pd, base_quaternion=qn,
+                              joint_positions=d.joint_positions + t * d.joint_velocities)  # fmt: skip
+    return out.update_caches(model)

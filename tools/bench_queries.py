@@ -3,7 +3,8 @@
 (`tests/test_benchmark.py:39-152`: one function per benchmark, batch of states, `jax.block_until_ready`): forward
 dynamics (ABA), bias forces (RNEA at zero acceleration), inverse dynamics, gravity torques, forward kinematics,
 mass matrix (CRBA), mass-matrix inverse, the full Jacobian + its derivative, the centroidal record (with and without the
-centroidal momentum matrix, beside the CRBA + kinematics launches it replaces) -- and the step kernels beside them.
+centroidal momentum matrix, beside the CRBA + kinematics launches it replaces), the Coriolis matrix (with and without the
+mass matrix of the same launch, beside the host composition over MODE_JAC it replaces) -- and the step kernels beside them.
 State resident in HBM, HIP events on the launch stream around `--reps` launches, the 24-link humanoid of the
 headline (`bench.build_model`), both precisions.  Per launch: time, batch / time, and the HBM bytes the launch has
 to move (state in + result out, algorithmic) against 8 TB/s.
@@ -77,6 +78,23 @@ for dtype in (np.float32, np.float64):
     T4 = jf.Targets(dm, np.array([nL - 1, nL - 2, nL // 2, 1]), H4)
     FR4, FJ4 = buf(4 * 24), buf(4 * 6 * nv)
 
+    Cc = buf(nv * nv)  # Coriolis matrix (MODE_CORIOLIS)
+    L_M_L = jsm.link_spatial_inertia_matrices(model)
+
+    def coriolis_host_path():  # what MODE_CORIOLIS replaces: MODE_JAC, downloaded, C_B = sum over links in NumPy
+        data._invalidate_caches()
+        B_J, B_Jd, B_H_L = jsm.jacobian_full_doubly_left(model, data)
+        mask = jsm._support_mask(model)[None, :, None, :]
+        L_X_B, B_X_L = jsm._adjoint(B_H_L, inverse=True), jsm._adjoint(B_H_L)
+        J = L_X_B @ (mask * B_J[:, None])
+        nu = np.concatenate([np.asarray(data._base_velocity_batched(jsm.VelRepr.Body)),
+                             np.asarray(data._fields()["joint_velocities"], np.float64).reshape(N, n)], -1)
+        v = np.einsum("nlij,nj->nli", J, nu)
+        Jd = -L_X_B @ jsm._vx_matrix(np.einsum("nlij,nlj->nli", B_X_L, v) - nu[:, None, :6]) @ (mask * B_J[:, None]) + L_X_B @ (mask * B_Jd[:, None])
+        X = jsm._vx_matrix(v)
+        K = -np.swapaxes(X, -1, -2) @ L_M_L + L_M_L @ X
+        return np.einsum("nlai,nlab->nib", J, K @ J + L_M_L @ Jd)
+
     def host_path():  # what the record replaces: MODE_KIN + MODE_JAC, downloaded, masked and re-expressed per link
         data._invalidate_caches()
         jsm.generalized_free_floating_jacobian(model, data)
@@ -104,6 +122,8 @@ for dtype in (np.float32, np.float64):
         ("MODE_KIN + MODE_JAC (what MODE_FRAMES replaces)",
          lambda: lib.jxs_refresh_kinematics(dm.handle, sp, HT, HV, N, stream.handle) or lib.jxs_jacobian_full(dm.handle, sp, J, HT, N, stream.handle),
          2 * rows_state + nL * 18 + 2 * 6 * nv + nL * 12),
+        ("coriolis (MODE_CORIOLIS)", lambda: lib.jxs_coriolis(dm.handle, sp, Cc, None, N, stream.handle), rows_state + nv * nv),
+        ("coriolis + M (MODE_CORIOLIS)", lambda: lib.jxs_coriolis(dm.handle, sp, Cc, M, N, stream.handle), rows_state + 2 * nv * nv),
         ("step, out of place (MODE_STEP)", lambda: lib.jxs_step(dm.handle, sp, scratch, None, None, 2, N, stream.handle), 2 * rows_state),
     ]
     # the host path MODE_FRAMES replaces: MODE_KIN + MODE_JAC, downloaded, masked and re-expressed per link on the host
@@ -115,6 +135,14 @@ for dtype in (np.float32, np.float64):
         host_path()
         t_host.append((time.perf_counter() - t0) * 1e6)
     print(f"  {'host path MODE_FRAMES replaces (KIN+JAC+NumPy)':44s} {np.dtype(dtype).name[-2:]:>5s} {float(np.median(t_host)):10.2f} {N / float(np.median(t_host)):9.1f}", flush=True)
+    # the host composition MODE_CORIOLIS replaces: MODE_JAC, downloaded, the reference's per-link sum in NumPy (body-fixed)
+    coriolis_host_path()
+    t_host = []
+    for _ in range(3):
+        t0 = time.perf_counter()
+        coriolis_host_path()
+        t_host.append((time.perf_counter() - t0) * 1e6)
+    print(f"  {'host path MODE_CORIOLIS replaces (JAC+NumPy)':44s} {np.dtype(dtype).name[-2:]:>5s} {float(np.median(t_host)):10.2f} {N / float(np.median(t_host)):9.1f}", flush=True)
 
     for name, call, rows_moved in cases:
         for _ in range(20):
