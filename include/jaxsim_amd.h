@@ -359,6 +359,19 @@ int jxs_centroidal(jxs_model* model, const void* state, void* out_record, void* 
  * is allocated and the host does not wait (legal inside a stream capture).                               */
 int jxs_coriolis(jxs_model* model, const void* state, void* out_C, void* out_M, int N, void* stream);
 
+/* forward_dynamics_crb (src/jaxsim/api/model.py:1409-1498): same arguments, layout and meaning as
+ * jxs_forward_dynamics_aba; M nu_dot = B tau - h + J^T f solved by CRBA + tree-sparse LtDL, one launch.  M (the
+ * composite-inertia sweep of jxs_mass_matrix) and its factor stay in the LDS, the right-hand side is one RNEA pass at zero
+ * acceleration with the link wrenches applied (h as free_floating_bias_forces: a fixed base drops its stored base
+ * velocity).  Like the reference's CRB path the link wrenches act through the link Jacobians: for a model whose base link
+ * has a pose offset, Body / Mixed wrenches are applied at the link frame of the dynamics, not of the cached kinematics
+ * (where jxs_forward_dynamics_aba converts them).  out_acc = [6+n][N]: inertial-fixed base acceleration (exactly zero for
+ * a fixed base), then the joint accelerations; every entry is written by the kernel -- no memset, nothing is allocated
+ * and the host does not wait (legal inside a stream capture).  Refused with JXS_EINVAL: a null out_acc, model or state,
+ * N <= 0.                                                                                                              */
+int jxs_forward_dynamics_crb(jxs_model* model, const void* state, const void* joint_forces, const void* link_forces,
+                             int force_repr, void* out_acc, int N, void* stream);
+
 /* Frames: poses, velocities, bias accelerations and Jacobians of frames rigidly attached to links, one launch
  * (jaxsim.api.link: transform, velocity, jacobian, bias_acceleration; jaxsim.api.frame: transform, velocity, jacobian;
  * jaxsim.api.model.link_bias_accelerations, src/jaxsim/api/model.py:2179-2395).  A target is (parent link L, L_H_F); a

@@ -319,20 +319,25 @@ def _vx(v6: np.ndarray, x6: np.ndarray) -> np.ndarray:
     return np.concatenate([np.cross(w, x6[:, :3]) + np.cross(v, x6[:, 3:]), np.cross(w, x6[:, 3:])], -1)
 
 
-def forward_dynamics_aba(model: JaxSimModel, data: JaxSimModelData, *, joint_forces=None, link_forces=None):
-    """``forward_dynamics_aba`` (``src/jaxsim/api/model.py:1269-1406``): base acceleration in
-    the active representation of ``data`` and joint accelerations."""
+def _forward_dynamics_device(model: JaxSimModel, data: JaxSimModelData, entry: str, joint_forces, link_forces):
+    """The shared body of ``forward_dynamics_aba`` / ``forward_dynamics_crb``: inputs to the device, one launch of the C
+    entry point ``entry`` (both take the same arguments), the inertial-fixed base acceleration of the kernel moved to the
+    active representation of ``data`` (``to_active``)."""
     dm = runtime.device_model(model, data.dtype)
+    if entry == "jxs_forward_dynamics_crb":
+        from .. import specialize
+
+        specialize.ensure_mode(dm, model, specialize.MODE_FD_CRB)  # (first call: cached object, or built when hipcc is there)
     N, nL, n = data.batch_size, model.number_of_links(), model.dofs()
     f = _as_device(link_forces, nL * 6, N, data.dtype, (nL, 6), data._state.tile)
     tau = _as_device(joint_forces, n, N, data.dtype, (n,), data._state.tile)
     out = DeviceArray(6 + n, N, data.dtype, tile=data._state.tile)
     _lib.check(
-        _lib.load().jxs_forward_dynamics_aba(
+        getattr(_lib.load(), entry)(
             dm.handle, C.c_void_p(data._state.ptr), _ptr(tau), _ptr(f), int(data.velocity_representation),
             C.c_void_p(out.ptr), N, runtime._sp(),
         ),
-        "jxs_forward_dynamics_aba",
+        entry,
     )  # fmt: skip
     res = out.to_host().T.astype(np.float64)
     W_vd, sdd = res[:, :6], res[:, 6:]
@@ -343,6 +348,34 @@ def forward_dynamics_aba(model: JaxSimModel, data: JaxSimModelData, *, joint_for
     else:
         C_vd = np.zeros((N, 6))
     return data._out(C_vd.astype(data.dtype)), data._out(sdd.astype(data.dtype))
+
+
+def forward_dynamics_aba(model: JaxSimModel, data: JaxSimModelData, *, joint_forces=None, link_forces=None):
+    """``forward_dynamics_aba`` (``src/jaxsim/api/model.py:1269-1406``): base acceleration in
+    the active representation of ``data`` and joint accelerations."""
+    return _forward_dynamics_device(model, data, "jxs_forward_dynamics_aba", joint_forces, link_forces)
+
+
+def forward_dynamics_crb(model: JaxSimModel, data: JaxSimModelData, *, joint_forces=None, link_forces=None):
+    """``forward_dynamics_crb`` (``src/jaxsim/api/model.py:1409-1498``): ``M nu_dot = B tau - h + J^T f`` solved in ONE
+    launch (``jxs_forward_dynamics_crb``, ``MODE_FD_CRB``): the composite inertias of CRBA, one RNEA pass at zero
+    acceleration with the link wrenches applied, the tree-sparse ``L^T D L`` factorisation of ``M``.  Same return
+    convention as ``forward_dynamics_aba``.  Like the reference's CRB path the link wrenches act through the link
+    Jacobians: for a model whose base link has a pose offset that differs from ``forward_dynamics_aba`` when
+    ``link_forces`` are given in Body or Mixed representation."""
+    return _forward_dynamics_device(model, data, "jxs_forward_dynamics_crb", joint_forces, link_forces)
+
+
+def forward_dynamics(model: JaxSimModel, data: JaxSimModelData, *, joint_forces=None, link_forces=None, prefer_aba: bool = True):
+    """``forward_dynamics`` (``src/jaxsim/api/model.py:1231-1266``): ``forward_dynamics_aba``, or with
+    ``prefer_aba=False`` ``forward_dynamics_crb``."""
+    fn = forward_dynamics_aba if prefer_aba else forward_dynamics_crb
+    return fn(model, data, joint_forces=joint_forces, link_forces=link_forces)
+
+
+def total_mass(model: JaxSimModel) -> float:
+    """``total_mass`` (``src/jaxsim/api/model.py:888``): the sum of the link masses."""
+    return model.total_mass()
 
 
 def inverse_dynamics(model: JaxSimModel, data: JaxSimModelData, *, joint_accelerations=None,

@@ -102,6 +102,7 @@ hipError_t launch_mode(int mode, int G, const jxs::KParams<T>& P, const unsigned
     case jxs::MODE_CENTROIDAL: return launch_g<T, jxs::MODE_CENTROIDAL>(G, P, mblk, A, s);
     case jxs::MODE_FRAMES: return launch_g<T, jxs::MODE_FRAMES>(G, P, mblk, A, s);
     case jxs::MODE_CORIOLIS: return launch_g<T, jxs::MODE_CORIOLIS>(G, P, mblk, A, s);
+    case jxs::MODE_FD_CRB: return launch_g<T, jxs::MODE_FD_CRB>(G, P, mblk, A, s);
     default: return launch_g<T, jxs::MODE_KIN>(G, P, mblk, A, s);
   }
 }
@@ -808,6 +809,16 @@ int jxs_forward_dynamics_aba(jxs_model* model, const void* state, const void* jo
                              int force_repr, void* out_acc, int N, void* stream) {
   if (out_acc == nullptr) return fail(JXS_EINVAL, "null out_acc");
   return run_any(model, jxs::MODE_FD, state, nullptr, joint_forces, link_forces, force_repr, nullptr, out_acc, nullptr,
+                 nullptr, N, 1, stream);
+}
+int jxs_forward_dynamics_crb(jxs_model* model, const void* state, const void* joint_forces, const void* link_forces,
+                             int force_repr, void* out_acc, int N, void* stream) {
+  // [MODE_FD_CRB] the kernel writes every entry of out_acc: no memset, no allocation, no host wait (legal inside a capture)
+  if (out_acc == nullptr) return fail(JXS_EINVAL, "null out_acc");
+  if (model == nullptr) return fail(JXS_EINVAL, "null model");
+  if (state == nullptr) return fail(JXS_EINVAL, "null state");
+  if (N <= 0) return fail(JXS_EINVAL, "N must be positive");
+  return run_any(model, jxs::MODE_FD_CRB, state, nullptr, joint_forces, link_forces, force_repr, nullptr, out_acc, nullptr,
                  nullptr, N, 1, stream);
 }
 int jxs_system_dynamics(jxs_model* model, const void* state, const void* joint_torques, const void* link_forces,

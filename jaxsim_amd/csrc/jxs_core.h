@@ -560,8 +560,10 @@ struct Core {
             mw[k] = f6[3 + k];
           }
         }
+        // (forward_dynamics_crb applies the wrench through the link Jacobians, which know nothing of the base-link offset
+        // of quirk 12 -- api/model.py:1458-1483 -- where ABA / RNEA convert it with the cached link transforms)
 #pragma unroll
-        for (int k = 0; k < 3; ++k) arm[k] = r[k] + doff[k];
+        for (int k = 0; k < 3; ++k) arm[k] = (MODE == MODE_FD_CRB) ? r[k] : r[k] + doff[k];
         cross(arm, fw, t);
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
@@ -779,6 +781,10 @@ struct Core {
     }
     if (MODE == MODE_CORIOLIS) {
       coriolis(lane, level, child, jrow, is_joint, is_root, MA, S6, vl, va, vBc, om);
+      return;
+    }
+    if (MODE == MODE_FD_CRB) {
+      fd_crb(lane, level, parent, jump, child, jrow, is_joint, is_root, MA, S6, cl, ca, mass, cw, Ic, bl, ba, fl, fa, pB, tau);
       return;
     }
 
@@ -2582,6 +2588,28 @@ struct Core {
                    const VM& is_joint, const VM& is_root, const V* Sl, const V* Sa, const V* cl, const V* ca,
                    const V& mass, const V* cw, const V* Ic, const V* bl, const V* ba, const V* fl, const V* fa,
                    const V* pB) const {
+    V tq, f6[6];
+    rnea_sweeps(lane, jrow, level, jump, child, is_joint, is_root, Sl, Sa, cl, ca, mass, cw, Ic, bl, ba, fl, fa, pB, tq, f6);
+    if (A.out_tau != nullptr) ln.gstore(A.out_tau, jrow, tq, is_joint, P.n);
+    if (A.out_a == nullptr) return;
+    ln.gstore(A.out_a, jrow + 6, tq, is_joint, 6 + P.n);
+    // W_f0 = B_X_W^T f_0: move the base wrench from the C origin back to the world origin
+    V t[3];
+    cross(pB, f6, t);
+    const VI zl = lane * 0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      ln.gstore(A.out_a, zl + k, f6[k], is_root, 6 + P.n);
+      ln.gstore(A.out_a, zl + (3 + k), f6[3 + k] + t[k], is_root, 6 + P.n);
+    }
+  }
+  // The two sweeps of RNEA -- accelerations root to leaves, wrenches leaves to root -- without the stores: `tq` = S . f of
+  // this lane's joint, `f6` = the wrench its link transmits (the base wrench about the origin of C in the root lane; zero
+  // there for a fixed base).  Shared by rnea() and fd_crb().
+  JXS_HD void rnea_sweeps(const VI& lane, const VI& jrow, const VI& level, const VI* jump, const VI* child,
+                          const VM& is_joint, const VM& is_root, const V* Sl, const V* Sa, const V* cl, const V* ca,
+                          const V& mass, const V* cw, const V* Ic, const V* bl, const V* ba, const V* fl, const V* fa,
+                          const V* pB, V& tq, V* f6) const {
     const V zero = V(T(0));
     const VI jrow_c = vsel(jrow >= 0, jrow, lane * 0);
     const V sdd = (A.in_a != nullptr) ? vsel(is_joint, ln.gload(A.in_a, jrow_c + 6, 6 + P.n), zero) : zero;
@@ -2608,7 +2636,6 @@ struct Core {
     }
     prefix6(jump, al, aa);  // a_i = a_lambda + S sdd + v x vJ  (rnea.py:150-152)
     // f_i = M a + v x* M v - f_ext  (rnea.py:163-168)
-    V f6[6];
     {
       V t[3], Ml[3], Ma_[3];
       cross(aa, cw, t);
@@ -2658,19 +2685,7 @@ struct Core {
         }
       }
     }
-    V tq = Sl[0] * f6[0] + Sl[1] * f6[1] + Sl[2] * f6[2] + Sa[0] * f6[3] + Sa[1] * f6[4] + Sa[2] * f6[5];
-    if (A.out_tau != nullptr) ln.gstore(A.out_tau, jrow, tq, is_joint, P.n);
-    if (A.out_a == nullptr) return;
-    ln.gstore(A.out_a, jrow + 6, tq, is_joint, 6 + P.n);
-    // W_f0 = B_X_W^T f_0: move the base wrench from the C origin back to the world origin
-    V t[3];
-    cross(pB, f6, t);
-    const VI zl = lane * 0;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      ln.gstore(A.out_a, zl + k, f6[k], is_root, 6 + P.n);
-      ln.gstore(A.out_a, zl + (3 + k), f6[3 + k] + t[k], is_root, 6 + P.n);
-    }
+    tq = Sl[0] * f6[0] + Sl[1] * f6[1] + Sl[2] * f6[2] + Sa[0] * f6[3] + Sa[1] * f6[4] + Sa[2] * f6[5];
   }
 
   // ==========================================================================================
@@ -2683,7 +2698,14 @@ struct Core {
   // out_a[(6+n)^2][N] is zeroed by the caller; only the structurally non-zero entries are written.
   JXS_HD void crba(const VI& lane, const VI& level, const VI* child, const VI& jrow, const VM& is_joint,
                    const VM& is_root, const V* M_link, const V* S6) const {
-    V Ic[21];
+    V Ic[21], F[6];
+    composite_inertia(lane, level, child, M_link, S6, Ic, F);
+    crba_store(lane, jrow, is_joint, is_root, S6, Ic, F);
+  }
+  // The leaves-to-base sweep of CRBA without the stores: `Ic` = composite inertia of this lane's subtree (upper triangle),
+  // `F` = Ic S of its joint.  Shared by crba() and fd_crb().
+  JXS_HD void composite_inertia(const VI& lane, const VI& level, const VI* child, const V* M_link, const V* S6, V* Ic,
+                                V* F) const {
 #pragma unroll
     for (int e = 0; e < 21; ++e) Ic[e] = M_link[e];
     // composite inertias, leaves to base: parents at level Lv-1 add their children (all at level Lv, final)
@@ -2720,7 +2742,6 @@ struct Core {
         }
       }
     }
-    V F[6];
 #pragma unroll
     for (int i = 0; i < 6; ++i) {
       V acc = Ic[sidx(i, 0)] * S6[0];
@@ -2728,6 +2749,9 @@ struct Core {
       for (int j = 1; j < 6; ++j) acc = acc + Ic[sidx(i, j)] * S6[j];
       F[i] = acc;
     }
+  }
+  JXS_HD void crba_store(const VI& lane, const VI& jrow, const VM& is_joint, const VM& is_root, const V* S6, const V* Ic,
+                         const V* F) const {
     const int nv = 6 + P.n, rows = nv * nv;
     const VI sub = ln.lconsti(A.lti, LI_SUBTREE);
     // base block: the composite inertia of the whole tree
@@ -3100,6 +3124,140 @@ struct Core {
         }
       }
     }
+  }
+
+  // ==========================================================================================
+  // forward_dynamics_crb (api/model.py:1409-1498): M nu_dot = B tau - h + J^T f, everything in frame C.
+  //   * M: the composite-inertia sweep of crba() (composite_inertia); row i = [F_i = Ic_i S_i | S_j . F_i for the
+  //     ancestor-or-self joints j of i], kept in the LDS (jxs_params.h fdcrb_*: one row per link, columns by tree level).
+  //   * b = B tau - h + J^T f: ONE RNEA pass at zero acceleration with the external link wrenches applied (rnea_sweeps):
+  //     b_i = tau_i - S_i . f_i, base rows -f_0.  No Jacobian is formed.  h is free_floating_bias_forces': gravity
+  //     included, and for a fixed base without the stored base velocity (run() starts the link velocities from zero).
+  //   * M = L^T D L, tree-sparse (Featherstone, RBDA 6.5): the joints are eliminated from the leaves towards the base, in
+  //     reverse lane order (depth-first: every descendant of a link sits in a higher lane).  Pivot k changes the rows of
+  //     its ancestors i only -- row_i -= (M[k, i] / D_k) row_k over the columns [F | b | ancestors of i], D_i -= M[k, i]^2 /
+  //     D_k -- so every ancestor lane updates its OWN row from one broadcast read of row k: no fill-in, no write conflicts.
+  //     The right-hand side rides along as a column (y = L^-T b).  The 6 x 6 base block I_0 - sum F_k F_k^T / D_k and its
+  //     right-hand side are accumulated in registers and solved last (solve6, the base solve of the ABA path); a fixed
+  //     base keeps the joint block only and a base acceleration of exactly zero (the reference's `else` branch).
+  //   * back-substitution base to leaves, in lane order: sdd_k = (y_k - F_k . a_0 - sum_j M[k, j] sdd_j) / D_k.
+  // The solution IS the acceleration (gravity sits in b), so the epilogue is MODE_FD's without the "+ g": out_a = [6+n][N],
+  // inertial-fixed base acceleration a_lin^C - wdot x p_B, then sdd; every entry is written.
+  JXS_HD void fd_crb(const VI& lane, const VI& level, const VI& parent, const VI* jump, const VI* child, const VI& jrow,
+                     const VM& is_joint, const VM& is_root, const V* M_link, const V* S6, const V* cl, const V* ca,
+                     const V& mass, const V* cw, const V* Ic3, const V* bl, const V* ba, const V* fl, const V* fa,
+                     const V* pB, const V& tau) const {
+    const V zero = V(T(0));
+    const VI zl = lane * 0;
+    V Ic[21], F[6];
+    composite_inertia(lane, level, child, M_link, S6, Ic, F);
+    V tq, f6[6];
+    rnea_sweeps(lane, jrow, level, jump, child, is_joint, is_root, S6, S6 + 3, cl, ca, mass, cw, Ic3, bl, ba, fl, fa, pB, tq, f6);
+    ln.stamp(A, 7);  // composite inertias + bias
+    // ---- the rows: head = [F (6) | b | D] stays in registers and is written through, the ancestor columns live in the LDS
+    const int Ws = fdcrb_row_words(P.max_depth), nq = Ws / 4;
+    const VI rowa = vsel(is_joint, lane, zl) * Ws;       // (the base and the lanes without a link: row 0, which nobody reads)
+    const VI lv1 = vsel(is_joint, level, zl + 1);        // >= 1
+    const VI colm = lv1 + 7;                             // where the rows BELOW this joint keep their entry with it
+    V head[8] = {F[0], F[1], F[2], F[3], F[4], F[5], vsel(is_joint, tau - tq, zero), zero};
+    {
+      const V z4[4] = {zero, zero, zero, zero};
+      for (int c = 2; c < nq; ++c) ln.template lds_writev<4>(rowa + 4 * c, z4);
+    }
+    VI j = lane;
+    for (int step = 0; step < P.max_depth; ++step) {  // j = the ancestor `step` links up: M[i, j] = S_j . F_i
+      V Sj[6];
+#pragma unroll
+      for (int e = 0; e < 6; ++e) Sj[e] = ln.shfl(S6[e], j);
+      const VI pj = ln.shfl(parent, j);
+      ln.fence();
+      V v = Sj[0] * F[0];
+#pragma unroll
+      for (int e = 1; e < 6; ++e) v = v + Sj[e] * F[e];
+      const VI lvj = lv1 - step;
+      const VM ok = is_joint && (lvj >= 1);
+      if (step == 0) head[7] = vsel(ok, v, zero);
+      else ln.lds_write(rowa + 7 + vsel(ok, lvj, zl + 1), v, ok);
+      j = vsel(ok && (pj >= 0), pj, zl);
+    }
+    ln.template lds_writev<8>(rowa, head);
+    ln.lds_sync();
+    ln.stamp(A, 8);  // rows of M in the LDS
+    // ---- L^T D L, leaves to base
+    const VI sub = ln.lconsti(A.lti, LI_SUBTREE);
+    V E[21], e6[6];
+#pragma unroll
+    for (int e = 0; e < 21; ++e) E[e] = zero;
+#pragma unroll
+    for (int e = 0; e < 6; ++e) e6[e] = zero;
+    for (int k = P.nL - 1; k >= 1; --k) {
+      const int rk = k * Ws;
+      V hk[8];
+      ln.template lds_readv<8>(zl + rk, hk);            // F_k, b_k, D_k: final, every deeper pivot is done
+      const V hki = ln.lds_read(colm + rk);             // M[k, i] for the ancestors i of k
+      const V invd = vsel(hk[7] == zero, zero, vrcp_acc(hk[7]));
+      const VM anc = is_joint && (lane < k) && (lane + sub > k);
+      const V a = vsel(anc, hki * invd, zero);
+#pragma unroll
+      for (int e = 0; e < 7; ++e) head[e] = head[e] - a * hk[e];
+      head[7] = head[7] - a * hki;
+      ln.template lds_writev<8>(rowa, head);
+      for (int c = 2; c < nq; ++c) {
+        V rk4[4], ri4[4];
+        ln.template lds_readv<4>(zl + (rk + 4 * c), rk4);
+        ln.template lds_readv<4>(rowa + 4 * c, ri4);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) ri4[e] = ri4[e] - a * rk4[e];
+        ln.template lds_writev<4>(rowa + 4 * c, ri4);
+      }
+      if (P.floating) {
+#pragma unroll
+        for (int i = 0; i < 6; ++i) {
+          const V fd = hk[i] * invd;
+#pragma unroll
+          for (int jj = i; jj < 6; ++jj) E[sidx(i, jj)] = E[sidx(i, jj)] + fd * hk[jj];
+          e6[i] = e6[i] + fd * hk[6];
+        }
+      }
+      ln.lds_sync();
+    }
+    ln.stamp(A, 9);  // factorisation
+    // ---- base block
+    V x0[6] = {zero, zero, zero, zero, zero, zero};
+    if (P.floating) {
+      V MA0[21], p0[6], a6[6];
+#pragma unroll
+      for (int e = 0; e < 21; ++e) MA0[e] = Ic[e] - E[e];
+#pragma unroll
+      for (int e = 0; e < 6; ++e) p0[e] = f6[e] + e6[e];
+      solve6(MA0, p0, a6);  // a_0 = -MA0^-1 p0, meaningful in the base lane only
+#pragma unroll
+      for (int e = 0; e < 6; ++e) x0[e] = ln.shfl(a6[e], zl);
+      ln.fence();
+    }
+    // ---- back-substitution, base to leaves
+    const V invd_own = vsel(is_joint && !(head[7] == zero), vrcp_acc(vsel(head[7] == zero, V(T(1)), head[7])), zero);
+    V acc = head[6];
+#pragma unroll
+    for (int e = 0; e < 6; ++e) acc = acc - head[e] * x0[e];
+    for (int i = 1; i < P.nL - 1; ++i) {  // (the last lane has no descendants)
+      const VI src = zl + i;
+      const V xi = ln.shfl(acc * invd_own, src);
+      const VI lvi = ln.shfl(lv1, src), subi = ln.shfl(sub, src);
+      ln.fence();
+      const VM desc = is_joint && (lane > i) && (lane < subi + i);
+      const V hki = ln.lds_read(rowa + 7 + lvi);
+      acc = acc - vsel(desc, hki * xi, zero);
+    }
+    const V sdd = acc * invd_own;
+    V t[3];
+    cross(x0 + 3, pB, t);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      ln.gstore(A.out_a, zl + k, x0[k] - t[k], is_root, 6 + P.n);
+      ln.gstore(A.out_a, zl + (3 + k), x0[3 + k], is_root, 6 + P.n);
+    }
+    ln.gstore(A.out_a, jrow + 6, sdd, is_joint, 6 + P.n);
   }
 
   // ==========================================================================================

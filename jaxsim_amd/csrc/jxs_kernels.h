@@ -101,6 +101,7 @@ __global__ __launch_bounds__(64, VARIANT == KV_OCC2 ? 2 : JXS_MIN_WAVES) void jx
   const jxs::DeviceLanes<T, G> ln(A.N, reinterpret_cast<T*>(jxs_smem),
                                   (MODE == jxs::MODE_STEP_RIGID || MODE == jxs::MODE_STEP_RK4_RIGID || MODE == jxs::MODE_DYN_RIGID) ? jxs::rigid_lds_words_per_env(P.n_cp, P.rigid, P.ct_tree, P.n_chunks, G)
                                   : MODE == jxs::MODE_STEP_RK4 ? jxs::rk4_lds_words_per_env(G, P.n_chunks)
+                                  : MODE == jxs::MODE_FD_CRB ? jxs::fdcrb_lds_words_per_env(P.nL, P.max_depth)
                                                                : jxs::lds_rows_words(G, P.nL));
   jxs::Core<jxs::DeviceLanes<T, G>> core(P, A, ln);
   core.template run<MODE>();
@@ -164,6 +165,9 @@ hipError_t launch_one(const jxs::KParams<T>& P, const unsigned char* mblk, const
   // (... and its row layout sits in an area of the G-wide upper bound, behind which the chunk data start: the kernel's
   // words per environment are rk4_lds_words_per_env in both cases)
   if (MODE == jxs::MODE_STEP_RK4 && (rows || P.n_chunks > 1)) lds_bytes = sizeof(T) * (size_t)envs_per_wave * jxs::rk4_lds_words_per_env(G, P.n_chunks);
+  // forward_dynamics_crb keeps the rows of the mass matrix and of its factor in the LDS (jxs_params.h fdcrb_*): at most
+  // 64 rows of 76 words, 38 KB in fp64 -- inside the default dynamic-LDS window
+  if (MODE == jxs::MODE_FD_CRB) lds_bytes = sizeof(T) * (size_t)envs_per_wave * jxs::fdcrb_lds_words_per_env(P.nL, P.max_depth);
   // (developer knobs arrive in A.knobs: the library reads the environment once, jxs_api.hip debug_knobs -- no getenv on the
   // launch path, no race with a Python thread that edits os.environ)
 #ifdef JXS_EXP_LDS_BYTES  // developer TIMING experiment only (results are garbage): allocate this many bytes whatever the kernel uses

@@ -250,9 +250,26 @@ enum Mode : int {
   // free-floating Coriolis matrix C(q, nu) in MIXED representation (api/model.py:1634-1745): one leaves-to-root sweep of
   // the composite inertia and of B_k = sum (v_L x*) M_L over the subtree, then the entries of every ancestor pair
   // (KArgs::out_a, [(6+n)^2][N]) and, on request, the mass matrix of the same launch (KArgs::out_H, jxs_mass_matrix layout)
-  MODE_CORIOLIS = 16
+  MODE_CORIOLIS = 16,
+  // forward_dynamics_crb (api/model.py:1409-1498): M nu_dot = B tau - h + J^T f with M from the composite-inertia sweep of
+  // CRBA, the right-hand side from ONE RNEA pass at zero acceleration with the external link wrenches applied, and the
+  // tree-sparse L^T D L factorisation of M (Featherstone, RBDA 6.5) in the LDS (fdcrb_*): a second forward-dynamics path
+  // beside the articulated-body recursion of MODE_FD.  Arguments and output (KArgs::out_a, [6+n][N]) as MODE_FD.
+  MODE_FD_CRB = 17
 };
-constexpr int kNumModes = 17;
+constexpr int kNumModes = 18;
+// MODE_FD_CRB: the factor of one environment in the LDS, one row of fdcrb_row_words per LINK (row = lane).  Row i holds
+//   [0, 6) the coupling F_i = Ic_i S_i with the base,  6 the right-hand side b_i,  7 the pivot D_i = M[i, i],
+//   7 + d the entry M[i, j] of the ancestor joint j of i at tree level d = 1 .. level(i) - 1  (7 + level(i): unused)
+// -- the ancestors of a link have distinct levels and a descendant shares them, so "column j" of every row below j is the
+// same word offset and the rows have no fill-in.  Row 0 (the base: its block stays in registers) takes the writes of the
+// lanes without a link.  Rows are whole 128-bit groups and an ODD number of them: the lanes of an environment read and
+// write their own rows with one address pattern, which an even stride would put on half the banks.
+JXS_HD constexpr int fdcrb_row_words(int max_depth) {
+  const int g = (8 + max_depth + 3) / 4;
+  return 4 * (g | 1);
+}
+JXS_HD constexpr int fdcrb_lds_words_per_env(int nL, int max_depth) { return nL * fdcrb_row_words(max_depth); }
 // MODE_CENTROIDAL: rows of the per-environment record (include/jaxsim_amd.h JXS_CENTROIDAL_*, checked there by jxs_api.hip)
 enum CentroidalRow : int {
   CR_COM = 0,         // 3: W_p_CoM

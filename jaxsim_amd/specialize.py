@@ -244,6 +244,7 @@ MODE_GRAV = 11
 MODE_CENTROIDAL = 14
 MODE_FRAMES = 15
 MODE_CORIOLIS = 16
+MODE_FD_CRB = 17  # forward_dynamics_crb: attached on first use (ensure_mode), not part of QUERY_MODES
 
 
 def ensure_mode(dm, model, mode: int) -> bool:

@@ -4,7 +4,8 @@
 dynamics (ABA), bias forces (RNEA at zero acceleration), inverse dynamics, gravity torques, forward kinematics,
 mass matrix (CRBA), mass-matrix inverse, the full Jacobian + its derivative, the centroidal record (with and without the
 centroidal momentum matrix, beside the CRBA + kinematics launches it replaces), the Coriolis matrix (with and without the
-mass matrix of the same launch, beside the host composition over MODE_JAC it replaces) -- and the step kernels beside them.
+mass matrix of the same launch, beside the host composition over MODE_JAC it replaces), forward dynamics through the
+equations of motion (MODE_FD_CRB, beside the CRBA + bias-force launches it replaces) -- and the step kernels beside them.
 State resident in HBM, HIP events on the launch stream around `--reps` launches, the 24-link humanoid of the
 headline (`bench.build_model`), both precisions.  Per launch: time, batch / time, and the HBM bytes the launch has
 to move (state in + result out, algorithmic) against 8 TB/s.
@@ -46,6 +47,10 @@ for dtype in (np.float32, np.float64):
 
         js.model.specialize(model, dtype, queries=True)
     dm = runtime.device_model(model, dtype)
+    if args.specialised:  # (forward_dynamics_crb is attached on first use, not with the query modes)
+        from jaxsim_amd import specialize
+
+        specialize.ensure_mode(dm, model, specialize.MODE_FD_CRB)
     lay = dm.layout
     tile = lay.tile
     Np = (N + tile - 1) // tile * tile
@@ -124,6 +129,10 @@ for dtype in (np.float32, np.float64):
          2 * rows_state + nL * 18 + 2 * 6 * nv + nL * 12),
         ("coriolis (MODE_CORIOLIS)", lambda: lib.jxs_coriolis(dm.handle, sp, Cc, None, N, stream.handle), rows_state + nv * nv),
         ("coriolis + M (MODE_CORIOLIS)", lambda: lib.jxs_coriolis(dm.handle, sp, Cc, M, N, stream.handle), rows_state + 2 * nv * nv),
+        ("forward_dynamics_crb (MODE_FD_CRB)", lambda: lib.jxs_forward_dynamics_crb(dm.handle, sp, None, None, 2, acc, N, stream.handle), rows_state + nv),
+        ("CRBA + bias forces (what MODE_FD_CRB replaces)",
+         lambda: lib.jxs_mass_matrix(dm.handle, sp, M, N, stream.handle) or lib.jxs_inverse_dynamics(dm.handle, sp, None, None, 2, frc, N, stream.handle),
+         2 * rows_state + nv * nv + nv),
         ("step, out of place (MODE_STEP)", lambda: lib.jxs_step(dm.handle, sp, scratch, None, None, 2, N, stream.handle), 2 * rows_state),
     ]
     # the host path MODE_FRAMES replaces: MODE_KIN + MODE_JAC, downloaded, masked and re-expressed per link on the host
