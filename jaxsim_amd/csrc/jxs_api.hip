@@ -168,12 +168,16 @@ struct jxs_model {
 
 namespace {
 
-template <typename T>
-ModelT<T>* typed(jxs_model* m);
-template <>
-ModelT<float>* typed<float>(jxs_model* m) { return m->f32.get(); }
-template <>
-ModelT<double>* typed<double>(jxs_model* m) { return m->f64.get(); }
+// the one fork on the precision: f(double{}) or f(float{}) for a dtype of the header, f(ModelT<double>*) or
+// f(ModelT<float>*) for a model -- both calls of the same return type
+template <typename F>
+auto with_dtype(int dtype, F&& f) {
+  return dtype == JXS_F64 ? f(double{}) : f(float{});
+}
+template <typename Model, typename F>
+auto with_typed(Model* model, F&& f) {
+  return model->dtype == JXS_F64 ? f(model->f64.get()) : f(model->f32.get());
+}
 
 template <typename T>
 int create_typed(const jxs_model_desc* d, std::unique_ptr<ModelT<T>>& slot) {
@@ -186,51 +190,93 @@ int create_typed(const jxs_model_desc* d, std::unique_ptr<ModelT<T>>& slot) {
   return JXS_OK;
 }
 
+// a tile-interleaved [rows][N] block: N rounded up to whole tiles of 64 / G environments
+size_t n_tiles(int N, int tile) { return (size_t)((N + tile - 1) / tile); }
+size_t tiled_elems(int N, int tile, size_t rows) { return n_tiles(N, tile) * tile * rows; }
 template <typename T>
-int run_typed(jxs_model* model, int mode, const void* state_in, void* state_out, const void* tau,
-              const void* link_f, int force_repr, const void* in_a, void* out_a, void* out_H, void* out_V, int N,
-              int repeat, void* stream, void* out_tau, bool fuse, int extra_flags, void* traj = nullptr, double fparam = 0.0) {
-  ModelT<T>* mt = typed<T>(model);
-  hipStream_t s = static_cast<hipStream_t>(stream);
+size_t tiled_bytes(const ModelT<T>* mt, int N, size_t rows) { return sizeof(T) * tiled_elems(N, 64 / mt->pk.G, rows); }
+size_t tiled_bytes(const jxs_model* model, int N, size_t rows) {
+  return with_typed(model, [&](auto* mt) { return tiled_bytes(mt, N, rows); });
+}
+
+// launch-flag bits an entry point may ask for (Launch::flags -> KArgs::flags; documented at KArgs::flags, jxs_params.h)
+constexpr int kFlagGravityCompensated = 1 << 1;  // gravity-compensated step of the rigid contact modes
+constexpr int kFlagTauSequence = 1 << 2;         // `tau` is a sequence, one [n][N] block of rows per step
+
+// One launch request: an entry point names the fields it uses, the rest keep their defaults.
+struct Launch {
+  int mode = jxs::MODE_KIN;
+  int N = 0;
+  const void* state_in = nullptr;
+  void* state_out = nullptr;
+  const void* tau = nullptr;     // joint forces / force references
+  const void* link_f = nullptr;  // link forces, in force_repr
+  int force_repr = 0;
+  const void* in_a = nullptr;
+  void *out_a = nullptr, *out_H = nullptr, *out_V = nullptr;  // what they hold depends on the mode (KArgs, jxs_params.h)
+  void* out_tau = nullptr;  // jxs_gravity_torques: joint torques only
+  int repeat = 1;           // MODE_STEP: steps, fused into one launch where that pays (run_typed)
+  bool fuse = true;         // false: one launch per step regardless (jxs_step_repeat)
+  int flags = 0;            // kFlag*
+  void* traj = nullptr;     // recorded rollout: [repeat * n_rows][N], the state after every step
+  double fparam = 0.0;      // MODE_DYN: Baumgarte gain
+  const void* tgt = nullptr;  // MODE_FRAMES: target table, and the velocity representations
+  int n_tgt = 0, in_repr = 0, out_repr = 0;
+};
+// what every request has, and the external forces in the order every entry point of the header takes them
+Launch request(int mode, const void* state_in, int N, const void* tau = nullptr, const void* link_f = nullptr, int force_repr = 0) {
+  Launch L;
+  L.mode = mode, L.state_in = state_in, L.N = N;
+  L.tau = tau, L.link_f = link_f, L.force_repr = force_repr;
+  return L;
+}
+
+// the model-specialised kernel of the mode if one is attached, else the library's own
+template <typename T>
+hipError_t dispatch(const ModelT<T>* mt, int mode, const jxs::KArgs<T>& a, hipStream_t s) {
+  return (mode >= 0 && mode < jxs::kNumModes && mt->spec_launch[mode] != nullptr)
+             ? static_cast<hipError_t>(mt->spec_launch[mode](&mt->pk.P, mt->mblk, &a, s))
+             : launch_mode<T>(mode, mt->pk.G, mt->pk.P, mt->mblk, a, s);
+}
+
+template <typename T>
+int run_typed(ModelT<T>* mt, const Launch& L, hipStream_t s) {
+  int mode = L.mode, repeat = L.repeat;
+  const int N = L.N, tile = 64 / mt->pk.G;
   jxs::KArgs<T> a = mt->args(N);
-  a.state_in = static_cast<const T*>(state_in);
-  a.state_out = static_cast<T*>(state_out);
-  a.tau = (mt->pk.P.n > 0) ? static_cast<const T*>(tau) : nullptr;  // no joints: nothing to read
-  a.link_f = static_cast<const T*>(link_f);
-  a.force_repr = force_repr;
-  a.in_a = static_cast<const T*>(in_a);
-  a.out_a = static_cast<T*>(out_a);
-  a.out_H = static_cast<T*>(out_H);
-  a.out_V = static_cast<T*>(out_V);
-  if (mode == jxs::MODE_STEP && state_out != state_in &&
-      (mt->pk.n_disabled > 0 || (mt->pk.P.rigid && mt->pk.P.n_points > 0))) {
-    // rows of disabled collidable points are not touched by the kernel, and the rigid contact models
-    // have no tangential deformation (their rows are passengers of the state block): carry them over
-    const int tile = 64 / mt->pk.G;
-    const size_t elems = (size_t)((N + tile - 1) / tile) * tile * mt->pk.P.n_rows;
-    JXS_HIP(hipMemcpyAsync(state_out, state_in, sizeof(T) * elems, hipMemcpyDeviceToDevice, s));
-  }
+  a.state_in = static_cast<const T*>(L.state_in);
+  a.state_out = static_cast<T*>(L.state_out);
+  a.tau = (mt->pk.P.n > 0) ? static_cast<const T*>(L.tau) : nullptr;  // no joints: nothing to read
+  a.link_f = static_cast<const T*>(L.link_f);
+  a.force_repr = L.force_repr;
+  a.in_a = static_cast<const T*>(L.in_a);
+  a.out_a = static_cast<T*>(L.out_a);
+  a.out_H = static_cast<T*>(L.out_H);
+  a.out_V = static_cast<T*>(L.out_V);
+  a.tgt = static_cast<const T*>(L.tgt);
+  a.n_tgt = L.n_tgt;
+  a.in_repr = L.in_repr;
+  a.out_repr = L.out_repr;
+  // rows of the state block the kernels do not write: those of disabled collidable points, and of every point of the
+  // rigid contact models (no tangential deformation: their rows are passengers of the block)
+  const bool passenger_rows = mt->pk.n_disabled > 0 || (mt->pk.P.rigid && mt->pk.P.n_points > 0);
+  if (mode == jxs::MODE_STEP && L.state_out != L.state_in && passenger_rows)  // carry them over
+    JXS_HIP(hipMemcpyAsync(L.state_out, L.state_in, tiled_bytes(mt, N, mt->pk.P.n_rows), hipMemcpyDeviceToDevice, s));
   if (mode == jxs::MODE_DYN) {
     if (mt->pk.P.rigid) mode = jxs::MODE_DYN_RIGID;
-    a.fparam = static_cast<T>(fparam);
-    // rows the kernel does not write: the deformation rates of disabled points, and of every point of the rigid contact
-    // models (no tangential state: their rows are passengers of the block) -- zero, like the reference's m_dot
-    if (state_out != nullptr && (mt->pk.n_disabled > 0 || (mt->pk.P.rigid && mt->pk.P.n_points > 0))) {
-      const int tile = 64 / mt->pk.G;
-      const size_t elems = (size_t)((N + tile - 1) / tile) * tile * mt->pk.P.n_rows;
-      JXS_HIP(hipMemsetAsync(state_out, 0, sizeof(T) * elems, s));
-    }
-    if (out_H != nullptr && mt->pk.P.n_chunks == 0) {  // no enabled points: the kernel has no contact phase
-      const int tile = 64 / mt->pk.G;
-      JXS_HIP(hipMemsetAsync(out_H, 0, sizeof(T) * (size_t)((N + tile - 1) / tile) * tile * mt->pk.P.nL * 6, s));
+    a.fparam = static_cast<T>(L.fparam);
+    // their deformation rates are zero, like the reference's m_dot
+    if (L.state_out != nullptr && passenger_rows) JXS_HIP(hipMemsetAsync(L.state_out, 0, tiled_bytes(mt, N, mt->pk.P.n_rows), s));
+    if (L.out_H != nullptr && mt->pk.P.n_chunks == 0) {  // no enabled points: the kernel has no contact phase
+      JXS_HIP(hipMemsetAsync(L.out_H, 0, tiled_bytes(mt, N, (size_t)mt->pk.P.nL * 6), s));
       a.out_H = nullptr;
-      if (state_out == nullptr) return JXS_OK;
+      if (L.state_out == nullptr) return JXS_OK;
     }
   }
   a.dbg = g_dbg;
-  a.flags |= extra_flags;
-  a.out_tau = static_cast<T*>(out_tau);  // jxs_gravity_torques: RNEA at zero velocity, joint torques only
-  a.id_zero_vel = out_tau != nullptr ? 1 : 0;
+  a.flags |= L.flags;
+  a.out_tau = static_cast<T*>(L.out_tau);  // jxs_gravity_torques: RNEA at zero velocity, joint torques only
+  a.id_zero_vel = L.out_tau != nullptr ? 1 : 0;
   a.n_steps = 1;
   if (mode == jxs::MODE_STEP && mt->pk.integrator == JXS_INTEGRATOR_RUNGE_KUTTA4) {
     // four dynamics evaluations per launch; a rollout is one launch per step
@@ -247,26 +293,25 @@ int run_typed(jxs_model* model, int mode, const void* state_in, void* state_out,
     if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
     return 4 * (cus > 0 ? cus : 256);
   }();
-  const int blocks = (N + (64 / mt->pk.G) - 1) / (64 / mt->pk.G);
-  const bool worth_fusing = traj != nullptr || blocks <= 8 * n_simds;
-  if (fuse && worth_fusing && mode == jxs::MODE_STEP && repeat > 1 && mt->pk.P.n_chunks <= 1 && (traj == nullptr || mt->pk.n_disabled == 0)) {
+  const int blocks = (N + tile - 1) / tile;
+  const bool worth_fusing = L.traj != nullptr || blocks <= 8 * n_simds;
+  if (L.fuse && worth_fusing && mode == jxs::MODE_STEP && repeat > 1 && mt->pk.P.n_chunks <= 1 && (L.traj == nullptr || mt->pk.n_disabled == 0)) {
     // fused rollout: one launch, the state stays in registers between the steps
     a.n_steps = repeat;
     repeat = 1;
     mode = jxs::MODE_ROLLOUT;
-    if (traj != nullptr) a.out_a = static_cast<T*>(traj);  // recorded: the kernel stores the state after every step (jxs_core.h)
+    if (L.traj != nullptr) a.out_a = static_cast<T*>(L.traj);  // recorded: the kernel stores the state after every step (jxs_core.h)
   }
-  const bool tau_seq = (extra_flags & 4) != 0 && a.tau != nullptr;
-  void* scratch = nullptr;  // the torques of the current step, [n][N] (one launch per step)
+  // one launch per step (RungeKutta4, the rigid contact models, several point chunks): the torques of step `it` are
+  // rows it * n ... of every tile of the sequence [n_steps * n][N] -- gathered into a [n][N] block per step (a strided
+  // device copy), which the step kernel reads like any joint_force_references
+  const bool gather_tau = (L.flags & kFlagTauSequence) != 0 && a.tau != nullptr && mode != jxs::MODE_ROLLOUT;
+  void* scratch = nullptr;  // the torques of the current step, [n][N]
   const T* const tau_all = a.tau;
   const int seq_steps = a.n_steps > 1 ? a.n_steps : repeat;
-  if (tau_seq && mode != jxs::MODE_ROLLOUT) {
-    // one launch per step (RungeKutta4, the rigid contact models, several point chunks): the torques of step `it` are
-    // rows it * n ... of every tile of the sequence [n_steps * n][N] -- gathered into a [n][N] block per step (a strided
-    // device copy), which the step kernel reads like any joint_force_references
-    a.flags &= ~4;
-    const int tile = 64 / mt->pk.G;
-    const size_t need = sizeof(T) * (size_t)((N + tile - 1) / tile) * tile * mt->pk.P.n;
+  if (gather_tau) {
+    a.flags &= ~kFlagTauSequence;
+    const size_t need = tiled_bytes(mt, N, mt->pk.P.n);
     // [ADVICE r4] one gather block per (model, STREAM), under a mutex: two streams or threads that roll out the same model
     // never share a block (round 4 kept one per model), and the launch path allocates only when a stream's block has to
     // grow -- which a stream capture cannot contain: refused there.  (hipMallocAsync / hipFreeAsync per call was tried
@@ -288,41 +333,54 @@ int run_typed(jxs_model* model, int mode, const void* state_in, void* state_out,
     scratch = blk.first;
   }
   for (int it = 0; it < repeat; ++it) {
-    if (tau_seq && mode != jxs::MODE_ROLLOUT) {
-      const int tile = 64 / mt->pk.G, n = mt->pk.P.n;
-      const size_t row_bytes = sizeof(T) * (size_t)tile;
-      JXS_HIP(hipMemcpy2DAsync(scratch, row_bytes * n, reinterpret_cast<const char*>(tau_all) + row_bytes * n * it,
-                               row_bytes * n * seq_steps, row_bytes * n, (size_t)((N + tile - 1) / tile), hipMemcpyDeviceToDevice, s));
+    if (gather_tau) {
+      const size_t step_bytes = sizeof(T) * (size_t)tile * mt->pk.P.n;
+      JXS_HIP(hipMemcpy2DAsync(scratch, step_bytes, reinterpret_cast<const char*>(tau_all) + step_bytes * it, step_bytes * seq_steps,
+                               step_bytes, n_tiles(N, tile), hipMemcpyDeviceToDevice, s));
       a.tau = static_cast<const T*>(scratch);
     }
-    hipError_t e = (mode >= 0 && mode < jxs::kNumModes && mt->spec_launch[mode] != nullptr)
-                       ? static_cast<hipError_t>(mt->spec_launch[mode](&mt->pk.P, mt->mblk, &a, s))
-                       : launch_mode<T>(mode, mt->pk.G, mt->pk.P, mt->mblk, a, s);
+    const hipError_t e = dispatch(mt, mode, a, s);
     if (e != hipSuccess) return hip_fail(e, "kernel launch");
-    if (traj != nullptr && mode != jxs::MODE_ROLLOUT) {
+    if (L.traj != nullptr && mode != jxs::MODE_ROLLOUT) {
       // recorded rollout, one launch per step: the state block after step `it` goes to rows it * n_rows ... of every tile
-      const int tile = 64 / mt->pk.G, rows = mt->pk.P.n_rows;
-      const size_t blk_bytes = sizeof(T) * (size_t)tile * rows;
-      JXS_HIP(hipMemcpy2DAsync(static_cast<char*>(traj) + blk_bytes * it, blk_bytes * seq_steps, a.state_out, blk_bytes, blk_bytes,
-                               (size_t)((N + tile - 1) / tile), hipMemcpyDeviceToDevice, s));
+      const size_t blk_bytes = sizeof(T) * (size_t)tile * mt->pk.P.n_rows;
+      JXS_HIP(hipMemcpy2DAsync(static_cast<char*>(L.traj) + blk_bytes * it, blk_bytes * seq_steps, a.state_out, blk_bytes, blk_bytes,
+                               n_tiles(N, tile), hipMemcpyDeviceToDevice, s));
     }
     if (it == 0 && repeat > 1) a.state_in = a.state_out;  // unfused rollout continues from its own output
   }
   return JXS_OK;
 }
 
-int run_any(jxs_model* model, int mode, const void* state_in, void* state_out, const void* tau, const void* link_f,
-            int force_repr, const void* in_a, void* out_a, void* out_H, void* out_V, int N, int repeat,
-            void* stream, void* out_tau = nullptr, bool fuse = true, int extra_flags = 0, void* traj = nullptr, double fparam = 0.0) {
+// the launch path of every entry point: its own checks come first, the common ones here
+int run(jxs_model* model, const Launch& L, void* stream) {
   if (model == nullptr) return fail(JXS_EINVAL, "null model");
-  if (state_in == nullptr) return fail(JXS_EINVAL, "null state");
-  if (N <= 0) return fail(JXS_EINVAL, "N must be positive");
-  if (force_repr < 0 || force_repr > 2) return fail(JXS_EINVAL, "invalid force representation");
-  if (model->dtype == JXS_F64)
-    return run_typed<double>(model, mode, state_in, state_out, tau, link_f, force_repr, in_a, out_a, out_H, out_V, N,
-                             repeat, stream, out_tau, fuse, extra_flags, traj, fparam);
-  return run_typed<float>(model, mode, state_in, state_out, tau, link_f, force_repr, in_a, out_a, out_H, out_V, N,
-                          repeat, stream, out_tau, fuse, extra_flags, traj, fparam);
+  if (L.state_in == nullptr) return fail(JXS_EINVAL, "null state");
+  if (L.N <= 0) return fail(JXS_EINVAL, "N must be positive");
+  if (L.force_repr < 0 || L.force_repr > 2) return fail(JXS_EINVAL, "invalid force representation");
+  return with_typed(model, [&](auto* mt) { return run_typed(mt, L, static_cast<hipStream_t>(stream)); });
+}
+
+// the matrix queries, whose kernels write only the structurally non-zero entries: L.out_a (and `also`, if given), tiled
+// [rows_of(6 + n)][N] blocks, are zeroed on the stream in front of the launch (the caller has checked the model, which is
+// not read before N is known to be good)
+template <typename Rows>
+int run_zeroed(jxs_model* model, const Launch& L, Rows rows_of, void* also, void* stream) {
+  if (L.N <= 0) return fail(JXS_EINVAL, "N must be positive");
+  const size_t nv = 6 + (size_t)with_typed(model, [](auto* mt) { return mt->pk.P.n; });
+  const size_t bytes = tiled_bytes(model, L.N, rows_of(nv));
+  JXS_HIP(hipMemsetAsync(L.out_a, 0, bytes, static_cast<hipStream_t>(stream)));
+  if (also != nullptr) JXS_HIP(hipMemsetAsync(also, 0, bytes, static_cast<hipStream_t>(stream)));
+  return run(model, L, stream);
+}
+size_t square(size_t nv) { return nv * nv; }
+
+// MODE_STEP from state_in to state_out, `repeat` times (the rollouts run in place)
+Launch step_request(const void* state_in, void* state_out, const void* tau, const void* link_forces, int force_repr, int N, int repeat) {
+  Launch L = request(jxs::MODE_STEP, state_in, N, tau, link_forces, force_repr);
+  L.state_out = state_out;
+  L.repeat = repeat;
+  return L;
 }
 
 // ---- RCCL, resolved lazily so that the library loads (and the CPU symbol test passes)
@@ -546,16 +604,13 @@ int jxs_model_create(const jxs_model_desc* desc, jxs_model** out) {
 int jxs_kernel_spec(const jxs_model_desc* desc, int mode, char* buf, int capacity) {
   if (desc == nullptr || buf == nullptr || capacity <= 0) return fail(JXS_EINVAL, "null argument");
   if (desc->dtype != JXS_F32 && desc->dtype != JXS_F64) return fail(JXS_EINVAL, "dtype must be JXS_F32 or JXS_F64");
-  std::string text, err;
-  if (desc->dtype == JXS_F64) {
-    jxs::Packed<double> pk;
-    err = jxs::pack_model<double>(*desc, pk);
-    if (err.empty()) text = jxs::kernel_spec_string(pk, mode);
-  } else {
-    jxs::Packed<float> pk;
-    err = jxs::pack_model<float>(*desc, pk);
-    if (err.empty()) text = jxs::kernel_spec_string(pk, mode);
-  }
+  std::string text;
+  const std::string err = with_dtype(desc->dtype, [&](auto zero) {
+    jxs::Packed<decltype(zero)> pk;
+    const std::string e = jxs::pack_model<decltype(zero)>(*desc, pk);
+    if (e.empty()) text = jxs::kernel_spec_string(pk, mode);
+    return e;
+  });
   if (!err.empty()) return fail(JXS_EINVAL, err);
   if ((int)text.size() + 1 > capacity) return fail(JXS_EINVAL, "buffer too small for the kernel description");
   std::memcpy(buf, text.c_str(), text.size() + 1);
@@ -565,17 +620,16 @@ int jxs_kernel_spec(const jxs_model_desc* desc, int mode, char* buf, int capacit
 int jxs_model_attach_specialized(jxs_model* model, int mode, const char* path) {
   if (model == nullptr || path == nullptr) return fail(JXS_EINVAL, "null argument");
   if (mode < 0 || mode >= jxs::kNumModes) return fail(JXS_EINVAL, "invalid mode");
-  return model->dtype == JXS_F64 ? attach_typed<double>(model, model->f64.get(), mode, path)
-                                 : attach_typed<float>(model, model->f32.get(), mode, path);
+  return with_typed(model, [&](auto* mt) { return attach_typed(model, mt, mode, path); });
 }
 int jxs_model_specialized_modes(const jxs_model* model, unsigned* mask) {
   if (model == nullptr || mask == nullptr) return fail(JXS_EINVAL, "null argument");
-  unsigned m = 0;
-  for (int k = 0; k < jxs::kNumModes; ++k) {
-    const bool on = model->dtype == JXS_F64 ? model->f64->spec_launch[k] != nullptr : model->f32->spec_launch[k] != nullptr;
-    if (on) m |= 1u << k;
-  }
-  *mask = m;
+  *mask = with_typed(model, [](auto* mt) {
+    unsigned m = 0;
+    for (int k = 0; k < jxs::kNumModes; ++k)
+      if (mt->spec_launch[k] != nullptr) m |= 1u << k;
+    return m;
+  });
   return JXS_OK;
 }
 
@@ -585,12 +639,11 @@ int jxs_model_destroy(jxs_model* model) {
 }
 int jxs_model_layout(const jxs_model* model, jxs_layout* out) {
   if (model == nullptr || out == nullptr) return fail(JXS_EINVAL, "null argument");
-  auto fill = [&](const auto& pk) {
-    const auto& P = pk.P;
+  with_typed(model, [&](auto* mt) {
+    const auto& P = mt->pk.P;
     *out = jxs_layout{P.nL, P.n, P.n_points, P.n_rows, P.row_pos, P.row_quat, P.row_s,
-                      P.row_vlin, P.row_vang, P.row_sd, P.row_m, pk.G, 64 / pk.G, model->dtype, P.row_mode};
-  };
-  if (model->dtype == JXS_F64) fill(model->f64->pk); else fill(model->f32->pk);
+                      P.row_vlin, P.row_vang, P.row_sd, P.row_m, mt->pk.G, 64 / mt->pk.G, model->dtype, P.row_mode};
+  });
   return JXS_OK;
 }
 
@@ -605,15 +658,13 @@ int jxs_validate_state(jxs_model* model, const void* state, int N, int* counts3,
     (void)hipFree(d);
     return hip_fail(e, "jxs_validate_state");
   }
-  jxs_layout lay;
-  jxs_model_layout(model, &lay);
   const int threads = 256, blocks = (N + threads - 1) / threads;
-  if (model->dtype == JXS_F64)
-    hipLaunchKernelGGL(jxs_validate_kernel<double>, dim3(blocks), dim3(threads), 0, s, static_cast<const double*>(state),
-                       lay.n_rows, lay.row_quat, lay.tile, N, d);
-  else
-    hipLaunchKernelGGL(jxs_validate_kernel<float>, dim3(blocks), dim3(threads), 0, s, static_cast<const float*>(state),
-                       lay.n_rows, lay.row_quat, lay.tile, N, d);
+  with_typed(model, [&](auto* mt) {
+    using T = typename std::remove_pointer_t<decltype(mt)>::value_type;
+    const auto& P = mt->pk.P;
+    hipLaunchKernelGGL(jxs_validate_kernel<T>, dim3(blocks), dim3(threads), 0, s, static_cast<const T*>(state), P.n_rows, P.row_quat,
+                       64 / mt->pk.G, N, d);
+  });
   e = hipGetLastError();
   if (e == hipSuccess) e = hipMemcpyAsync(counts3, d, 3 * sizeof(int), hipMemcpyDeviceToHost, s);
   if (e == hipSuccess) e = hipStreamSynchronize(s);
@@ -630,13 +681,11 @@ static int retile(const void* src, void* dst, int rows, int N, int tile, int dty
   const long long total = (long long)rows * N;
   const int threads = 256;
   const int blocks = (int)((total + threads - 1) / threads);
-  if (dtype == JXS_F64) {
-    if (to_tiled) hipLaunchKernelGGL((jxs_retile_kernel<double, true>), dim3(blocks), dim3(threads), 0, s, (const double*)src, (double*)dst, rows, N, tile);
-    else hipLaunchKernelGGL((jxs_retile_kernel<double, false>), dim3(blocks), dim3(threads), 0, s, (const double*)src, (double*)dst, rows, N, tile);
-  } else {
-    if (to_tiled) hipLaunchKernelGGL((jxs_retile_kernel<float, true>), dim3(blocks), dim3(threads), 0, s, (const float*)src, (float*)dst, rows, N, tile);
-    else hipLaunchKernelGGL((jxs_retile_kernel<float, false>), dim3(blocks), dim3(threads), 0, s, (const float*)src, (float*)dst, rows, N, tile);
-  }
+  with_dtype(dtype, [&](auto zero) {
+    using T = decltype(zero);
+    if (to_tiled) hipLaunchKernelGGL((jxs_retile_kernel<T, true>), dim3(blocks), dim3(threads), 0, s, (const T*)src, (T*)dst, rows, N, tile);
+    else hipLaunchKernelGGL((jxs_retile_kernel<T, false>), dim3(blocks), dim3(threads), 0, s, (const T*)src, (T*)dst, rows, N, tile);
+  });
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return hip_fail(e, "jxs_retile");
   return JXS_OK;
@@ -651,34 +700,32 @@ int jxs_tile_to_env_major(const void* src, void* dst, int rows, int N, int tile,
 int jxs_step(jxs_model* model, const void* state_in, void* state_out, const void* tau, const void* link_forces,
              int force_repr, int N, void* stream) {
   if (state_out == nullptr) return fail(JXS_EINVAL, "null state_out");
-  return run_any(model, jxs::MODE_STEP, state_in, state_out, tau, link_forces, force_repr, nullptr, nullptr, nullptr,
-                 nullptr, N, 1, stream);
+  return run(model, step_request(state_in, state_out, tau, link_forces, force_repr, N, 1), stream);
 }
 int jxs_step_gravity_compensated(jxs_model* model, const void* state_in, void* state_out, const void* tau,
                                  const void* link_forces, int force_repr, int N, void* stream) {
   if (state_out == nullptr) return fail(JXS_EINVAL, "null state_out");
   if (model == nullptr) return fail(JXS_EINVAL, "null model");
-  const bool rigid = model->dtype == JXS_F64 ? (model->f64->pk.P.rigid != 0) : (model->f32->pk.P.rigid != 0);
-  if (!rigid)
+  if (!with_typed(model, [](auto* mt) { return mt->pk.P.rigid != 0; }))
     return fail(JXS_EINVAL, "jxs_step_gravity_compensated: built for the rigid contact models (RigidContacts / RelaxedRigidContacts with "
                             "enabled points); use jxs_gravity_torques + jxs_step");
-  return run_any(model, jxs::MODE_STEP, state_in, state_out, tau, link_forces, force_repr, nullptr, nullptr, nullptr, nullptr, N, 1,
-                 stream, nullptr, true, 2);
+  Launch L = step_request(state_in, state_out, tau, link_forces, force_repr, N, 1);
+  L.flags = kFlagGravityCompensated;
+  return run(model, L, stream);
 }
 int jxs_rollout(jxs_model* model, void* state, const void* tau, const void* link_forces, int force_repr, int N,
                 int n_steps, void* stream) {
   if (n_steps < 0) return fail(JXS_EINVAL, "n_steps must be >= 0");
-  return run_any(model, jxs::MODE_STEP, state, state, tau, link_forces, force_repr, nullptr, nullptr, nullptr, nullptr,
-                 N, n_steps, stream);
+  return run(model, step_request(state, state, tau, link_forces, force_repr, N, n_steps), stream);
 }
 int jxs_rollout_controlled(jxs_model* model, void* state, const void* tau_seq, const void* link_forces, int force_repr,
                            int N, int n_steps, void* stream) {
   if (n_steps < 0) return fail(JXS_EINVAL, "n_steps must be >= 0");
   if (n_steps == 0) return JXS_OK;
   if (tau_seq == nullptr) return fail(JXS_EINVAL, "null torque sequence (jxs_rollout takes constant or no torques)");
-  if (n_steps == 1) return run_any(model, jxs::MODE_STEP, state, state, tau_seq, link_forces, force_repr, nullptr, nullptr, nullptr, nullptr, N, 1, stream);
-  return run_any(model, jxs::MODE_STEP, state, state, tau_seq, link_forces, force_repr, nullptr, nullptr, nullptr, nullptr,
-                 N, n_steps, stream, nullptr, /*fuse=*/true, /*extra_flags=*/4);
+  Launch L = step_request(state, state, tau_seq, link_forces, force_repr, N, n_steps);
+  if (n_steps > 1) L.flags = kFlagTauSequence;
+  return run(model, L, stream);
 }
 int jxs_rollout_recorded(jxs_model* model, void* state, const void* tau, int tau_per_step, const void* link_forces,
                          int force_repr, int N, int n_steps, void* out_states, void* stream) {
@@ -686,8 +733,10 @@ int jxs_rollout_recorded(jxs_model* model, void* state, const void* tau, int tau
   if (n_steps == 0) return JXS_OK;
   if (out_states == nullptr) return fail(JXS_EINVAL, "null out_states (jxs_rollout / jxs_rollout_controlled do not record)");
   if (tau_per_step && tau == nullptr) return fail(JXS_EINVAL, "tau_per_step without a torque sequence");
-  return run_any(model, jxs::MODE_STEP, state, state, tau, link_forces, force_repr, nullptr, nullptr, nullptr, nullptr,
-                 N, n_steps, stream, nullptr, /*fuse=*/true, /*extra_flags=*/(tau_per_step && n_steps > 1) ? 4 : 0, out_states);
+  Launch L = step_request(state, state, tau, link_forces, force_repr, N, n_steps);
+  if (tau_per_step && n_steps > 1) L.flags = kFlagTauSequence;
+  L.traj = out_states;
+  return run(model, L, stream);
 }
 int jxs_step_repeat(jxs_model* model, void* state, const void* tau, const void* link_forces, int force_repr, int N,
                     int n_launches, void* stream) {
@@ -695,6 +744,8 @@ int jxs_step_repeat(jxs_model* model, void* state, const void* tau, const void* 
   if (n_launches == 0) return JXS_OK;
   if (model == nullptr) return fail(JXS_EINVAL, "null model");
   if (state == nullptr) return fail(JXS_EINVAL, "null state");
+  Launch L = step_request(state, state, tau, link_forces, force_repr, N, n_launches);
+  L.fuse = false;
   // Blocks of launches are captured once into a hipGraph and replayed: the same kernels in the same
   // order, with less per-launch work on the host and smaller gaps on the device (9.94 -> 9.77 us per step
   // at 1024 humanoids with 50 launches per graph, 9.2 with 250).  Two block sizes: requests of 250 or more
@@ -732,8 +783,8 @@ int jxs_step_repeat(jxs_model* model, void* state, const void* tau, const void* 
         if (sl.exec != nullptr) (void)hipGraphExecDestroy(sl.exec), sl.exec = nullptr;
         hipGraph_t g = nullptr;
         JXS_HIP(hipStreamBeginCapture(hs, hipStreamCaptureModeThreadLocal));
-        const int rc = run_any(model, jxs::MODE_STEP, state, state, tau, link_forces, force_repr, nullptr, nullptr, nullptr,
-                               nullptr, N, block, stream, nullptr, /*fuse=*/false);
+        L.repeat = block;
+        const int rc = run(model, L, stream);
         hipError_t e = hipStreamEndCapture(hs, &g);
         if (rc != JXS_OK) {
           if (g != nullptr) (void)hipGraphDestroy(g);
@@ -752,8 +803,8 @@ int jxs_step_repeat(jxs_model* model, void* state, const void* tau, const void* 
     }
     if (n_launches == 0) return JXS_OK;
   }
-  return run_any(model, jxs::MODE_STEP, state, state, tau, link_forces, force_repr, nullptr, nullptr, nullptr, nullptr,
-                 N, n_launches, stream, nullptr, /*fuse=*/false);
+  L.repeat = n_launches;
+  return run(model, L, stream);
 }
 int jxs_step_repeat_timed(jxs_model* model, void* state, const void* tau, const void* link_forces, int force_repr, int N,
                           int n_launches, void* stream, double* seconds) {
@@ -805,54 +856,57 @@ int jxs_step_repeat_timed(jxs_model* model, void* state, const void* tau, const 
   *seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   return rc;
 }
+static int forward_dynamics(jxs_model* model, int mode, const void* state, const void* joint_forces, const void* link_forces,
+                            int force_repr, void* out_acc, int N, void* stream) {
+  if (out_acc == nullptr) return fail(JXS_EINVAL, "null out_acc");
+  Launch L = request(mode, state, N, joint_forces, link_forces, force_repr);
+  L.out_a = out_acc;
+  return run(model, L, stream);
+}
 int jxs_forward_dynamics_aba(jxs_model* model, const void* state, const void* joint_forces, const void* link_forces,
                              int force_repr, void* out_acc, int N, void* stream) {
-  if (out_acc == nullptr) return fail(JXS_EINVAL, "null out_acc");
-  return run_any(model, jxs::MODE_FD, state, nullptr, joint_forces, link_forces, force_repr, nullptr, out_acc, nullptr,
-                 nullptr, N, 1, stream);
+  return forward_dynamics(model, jxs::MODE_FD, state, joint_forces, link_forces, force_repr, out_acc, N, stream);
 }
 int jxs_forward_dynamics_crb(jxs_model* model, const void* state, const void* joint_forces, const void* link_forces,
                              int force_repr, void* out_acc, int N, void* stream) {
   // [MODE_FD_CRB] the kernel writes every entry of out_acc: no memset, no allocation, no host wait (legal inside a capture)
-  if (out_acc == nullptr) return fail(JXS_EINVAL, "null out_acc");
-  if (model == nullptr) return fail(JXS_EINVAL, "null model");
-  if (state == nullptr) return fail(JXS_EINVAL, "null state");
-  if (N <= 0) return fail(JXS_EINVAL, "N must be positive");
-  return run_any(model, jxs::MODE_FD_CRB, state, nullptr, joint_forces, link_forces, force_repr, nullptr, out_acc, nullptr,
-                 nullptr, N, 1, stream);
+  return forward_dynamics(model, jxs::MODE_FD_CRB, state, joint_forces, link_forces, force_repr, out_acc, N, stream);
+}
+// MODE_DYN: the state derivative (or null) and the inertial link contact wrenches (or null)
+static int run_dynamics(jxs_model* model, const void* state, const void* joint_torques, const void* link_forces, int force_repr,
+                        double baumgarte, void* out_xdot, void* out_link_contact_forces, int N, void* stream) {
+  Launch L = request(jxs::MODE_DYN, state, N, joint_torques, link_forces, force_repr);
+  L.state_out = out_xdot;
+  L.out_H = out_link_contact_forces;
+  L.fparam = baumgarte;
+  return run(model, L, stream);
 }
 int jxs_system_dynamics(jxs_model* model, const void* state, const void* joint_torques, const void* link_forces,
                         int force_repr, double baumgarte, void* out_xdot, void* out_link_contact_forces, int N, void* stream) {
   if (out_xdot == nullptr && out_link_contact_forces == nullptr) return fail(JXS_EINVAL, "jxs_system_dynamics: no output asked for");
   if (out_xdot != nullptr && out_xdot == state) return fail(JXS_EINVAL, "jxs_system_dynamics: out_xdot must not alias the state");
-  return run_any(model, jxs::MODE_DYN, state, out_xdot, joint_torques, link_forces, force_repr, nullptr, nullptr,
-                 out_link_contact_forces, nullptr, N, 1, stream, nullptr, true, 0, nullptr, baumgarte);
+  return run_dynamics(model, state, joint_torques, link_forces, force_repr, baumgarte, out_xdot, out_link_contact_forces, N, stream);
 }
 int jxs_link_contact_forces(jxs_model* model, const void* state, const void* joint_torques, const void* link_forces,
                             int force_repr, void* out_link_contact_forces, void* out_mdot, int N, void* stream) {
   if (out_link_contact_forces == nullptr) return fail(JXS_EINVAL, "null out_link_contact_forces");
   if (model == nullptr) return fail(JXS_EINVAL, "null model");
   if (N <= 0) return fail(JXS_EINVAL, "N must be positive");
-  if (out_mdot == nullptr)
-    return run_any(model, jxs::MODE_DYN, state, nullptr, joint_torques, link_forces, force_repr, nullptr, nullptr,
-                   out_link_contact_forces, nullptr, N, 1, stream, nullptr, true, 0, nullptr, 1.0);
-  // with the deformation rates: the derivative block goes to a scratch block and its rows of m are copied out (one
-  // strided device copy; the rows of the tangential deformation are the last 3 * n_points rows of every tile)
   jxs_layout lay;
   jxs_model_layout(model, &lay);
-  const size_t esz = model->dtype == JXS_F64 ? 8 : 4;
-  const size_t tiles = (size_t)((N + lay.tile - 1) / lay.tile);
+  if (out_mdot == nullptr || lay.n_points == 0)
+    return run_dynamics(model, state, joint_torques, link_forces, force_repr, 1.0, nullptr, out_link_contact_forces, N, stream);
+  // with the deformation rates: the derivative block goes to a scratch block and its rows of m are copied out (one
+  // strided device copy; the rows of the tangential deformation are the last 3 * n_points rows of every tile)
+  const size_t tile_bytes = (size_t)lay.tile * (model->dtype == JXS_F64 ? 8 : 4);  // of one row of a tile
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (lay.n_points == 0) return run_any(model, jxs::MODE_DYN, state, nullptr, joint_torques, link_forces, force_repr, nullptr, nullptr,
-                                        out_link_contact_forces, nullptr, N, 1, stream, nullptr, true, 0, nullptr, 1.0);
   void* xdot = nullptr;
-  JXS_HIP(hipMalloc(&xdot, tiles * lay.tile * lay.n_rows * esz));
-  int rc = run_any(model, jxs::MODE_DYN, state, xdot, joint_torques, link_forces, force_repr, nullptr, nullptr,
-                   out_link_contact_forces, nullptr, N, 1, stream, nullptr, true, 0, nullptr, 1.0);
+  JXS_HIP(hipMalloc(&xdot, tiled_bytes(model, N, lay.n_rows)));
+  int rc = run_dynamics(model, state, joint_torques, link_forces, force_repr, 1.0, xdot, out_link_contact_forces, N, stream);
   if (rc == JXS_OK) {
     const size_t mrows = 3 * (size_t)lay.n_points;
-    const hipError_t e = hipMemcpy2DAsync(out_mdot, esz * lay.tile * mrows, static_cast<const char*>(xdot) + esz * lay.tile * lay.row_m,
-                                          esz * lay.tile * lay.n_rows, esz * lay.tile * mrows, tiles, hipMemcpyDeviceToDevice, s);
+    const hipError_t e = hipMemcpy2DAsync(out_mdot, tile_bytes * mrows, static_cast<const char*>(xdot) + tile_bytes * lay.row_m,
+                                          tile_bytes * lay.n_rows, tile_bytes * mrows, n_tiles(N, lay.tile), hipMemcpyDeviceToDevice, s);
     if (e != hipSuccess) rc = hip_fail(e, "hipMemcpy2DAsync");
   }
   (void)hipStreamSynchronize(s);  // the scratch block is freed below
@@ -862,16 +916,19 @@ int jxs_link_contact_forces(jxs_model* model, const void* state, const void* joi
 int jxs_inverse_dynamics(jxs_model* model, const void* state, const void* in_acc, const void* link_forces,
                          int force_repr, void* out_forces, int N, void* stream) {
   if (out_forces == nullptr) return fail(JXS_EINVAL, "null out_forces");
-  return run_any(model, jxs::MODE_ID, state, nullptr, nullptr, link_forces, force_repr, in_acc, out_forces, nullptr,
-                 nullptr, N, 1, stream);
+  Launch L = request(jxs::MODE_ID, state, N, nullptr, link_forces, force_repr);
+  L.in_a = in_acc;
+  L.out_a = out_forces;
+  return run(model, L, stream);
 }
 int jxs_gravity_torques(jxs_model* model, const void* state, void* out_tau, int N, void* stream) {
   if (out_tau == nullptr) return fail(JXS_EINVAL, "null out_tau");
   // [round 3] a kernel of its own (MODE_GRAV) instead of the general RNEA evaluated at zero velocity: with v = 0 and
   // zero accelerations every link "accelerates" with -g, so the torques are subtree sums of the link weights --
   // no velocity rows, no prefix sums, no rotated inertias (jxs_core.h gravity_torques)
-  return run_any(model, jxs::MODE_GRAV, state, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, N, 1, stream,
-                 out_tau);
+  Launch L = request(jxs::MODE_GRAV, state, N);
+  L.out_tau = out_tau;
+  return run(model, L, stream);
 }
 int jxs_debug_reload_env(void) {
   int k, b;
@@ -881,7 +938,7 @@ int jxs_debug_reload_env(void) {
 }
 int jxs_solver_fault_counts(jxs_model* model, int* counts2, int reset, void* stream) {
   if (model == nullptr || counts2 == nullptr) return fail(JXS_EINVAL, "null argument");
-  int* d = model->dtype == JXS_F64 ? model->f64->faults : model->f32->faults;
+  int* d = with_typed(model, [](auto* mt) { return mt->faults; });
   hipStream_t s = static_cast<hipStream_t>(stream);
   JXS_HIP(hipMemcpyAsync(counts2, d, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
   if (reset) JXS_HIP(hipMemsetAsync(d, 0, 2 * sizeof(int), s));
@@ -891,58 +948,44 @@ int jxs_solver_fault_counts(jxs_model* model, int* counts2, int reset, void* str
 int jxs_mass_matrix(jxs_model* model, const void* state, void* out_M, int N, void* stream) {
   if (out_M == nullptr) return fail(JXS_EINVAL, "null out_M");
   if (model == nullptr) return fail(JXS_EINVAL, "null model");
-  if (N <= 0) return fail(JXS_EINVAL, "N must be positive");
-  jxs_layout lay;
-  jxs_model_layout(model, &lay);
-  const size_t nv = 6 + (size_t)lay.n_joints;
-  const size_t elems = (size_t)((N + lay.tile - 1) / lay.tile) * lay.tile * nv * nv;
-  // only the structurally non-zero entries are written by the kernel
-  JXS_HIP(hipMemsetAsync(out_M, 0, elems * (model->dtype == JXS_F64 ? 8 : 4), static_cast<hipStream_t>(stream)));
-  return run_any(model, jxs::MODE_CRBA, state, nullptr, nullptr, nullptr, 0, nullptr, out_M, nullptr, nullptr, N, 1, stream);
+  Launch L = request(jxs::MODE_CRBA, state, N);
+  L.out_a = out_M;  // only the structurally non-zero entries are written by the kernel
+  return run_zeroed(model, L, square, nullptr, stream);
 }
 int jxs_mass_matrix_inverse(jxs_model* model, const void* state, void* out_Minv, int N, void* stream) {
   if (out_Minv == nullptr) return fail(JXS_EINVAL, "null out_Minv");
   if (model == nullptr) return fail(JXS_EINVAL, "null model");
-  if (N <= 0) return fail(JXS_EINVAL, "N must be positive");
-  jxs_layout lay;
-  jxs_model_layout(model, &lay);
-  const size_t nv = 6 + (size_t)lay.n_joints;
-  const size_t elems = (size_t)((N + lay.tile - 1) / lay.tile) * lay.tile * nv * nv;
-  JXS_HIP(hipMemsetAsync(out_Minv, 0, elems * (model->dtype == JXS_F64 ? 8 : 4), static_cast<hipStream_t>(stream)));
-  return run_any(model, jxs::MODE_MINV, state, nullptr, nullptr, nullptr, 0, nullptr, out_Minv, nullptr, nullptr, N, 1, stream);
+  Launch L = request(jxs::MODE_MINV, state, N);
+  L.out_a = out_Minv;
+  return run_zeroed(model, L, square, nullptr, stream);
 }
 int jxs_jacobian_full(jxs_model* model, const void* state, void* out_J, void* out_B_H_L, int N, void* stream) {
   if (out_J == nullptr) return fail(JXS_EINVAL, "null out_J");
   if (model == nullptr) return fail(JXS_EINVAL, "null model");
-  if (N <= 0) return fail(JXS_EINVAL, "N must be positive");
-  jxs_layout lay;
-  jxs_model_layout(model, &lay);
-  const size_t nv = 6 + (size_t)lay.n_joints;
-  const size_t elems = (size_t)((N + lay.tile - 1) / lay.tile) * lay.tile * 12 * nv;
-  JXS_HIP(hipMemsetAsync(out_J, 0, elems * (model->dtype == JXS_F64 ? 8 : 4), static_cast<hipStream_t>(stream)));
-  return run_any(model, jxs::MODE_JAC, state, nullptr, nullptr, nullptr, 0, nullptr, out_J, out_B_H_L, nullptr, N, 1, stream);
+  Launch L = request(jxs::MODE_JAC, state, N);
+  L.out_a = out_J;
+  L.out_H = out_B_H_L;
+  return run_zeroed(model, L, [](size_t nv) { return 12 * nv; }, nullptr, stream);
 }
 int jxs_centroidal(jxs_model* model, const void* state, void* out_record, void* out_cmm, int N, void* stream) {
   // [MODE_CENTROIDAL] record and A_G: every entry is written by the kernel (no memset), nothing is allocated and the host
   // does not wait -- legal inside a stream capture
   if (out_record == nullptr) return fail(JXS_EINVAL, "null out_record");
-  return run_any(model, jxs::MODE_CENTROIDAL, state, nullptr, nullptr, nullptr, 0, nullptr, out_cmm, out_record, nullptr, N, 1, stream);
+  Launch L = request(jxs::MODE_CENTROIDAL, state, N);
+  L.out_a = out_cmm;
+  L.out_H = out_record;
+  return run(model, L, stream);
 }
 int jxs_coriolis(jxs_model* model, const void* state, void* out_C, void* out_M, int N, void* stream) {
   // [MODE_CORIOLIS] the kernel writes the structurally non-zero entries of C (and of M): both are zeroed first with
   // hipMemsetAsync, like jxs_mass_matrix -- nothing is allocated and the host does not wait (legal inside a stream capture)
   if (out_C == nullptr) return fail(JXS_EINVAL, "null out_C");
   if (model == nullptr) return fail(JXS_EINVAL, "null model");
-  if (state == nullptr) return fail(JXS_EINVAL, "null state");
-  if (N <= 0) return fail(JXS_EINVAL, "N must be positive");
-  jxs_layout lay;
-  jxs_model_layout(model, &lay);
-  const size_t nv = 6 + (size_t)lay.n_joints;
-  const size_t bytes = (size_t)((N + lay.tile - 1) / lay.tile) * lay.tile * nv * nv * (model->dtype == JXS_F64 ? 8 : 4);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  JXS_HIP(hipMemsetAsync(out_C, 0, bytes, s));
-  if (out_M != nullptr) JXS_HIP(hipMemsetAsync(out_M, 0, bytes, s));
-  return run_any(model, jxs::MODE_CORIOLIS, state, nullptr, nullptr, nullptr, 0, nullptr, out_C, out_M, nullptr, N, 1, stream);
+  if (state == nullptr) return fail(JXS_EINVAL, "null state");  // (reported in front of a bad N, and nothing is zeroed)
+  Launch L = request(jxs::MODE_CORIOLIS, state, N);
+  L.out_a = out_C;
+  L.out_H = out_M;
+  return run_zeroed(model, L, square, out_M, stream);
 }
 int jxs_frames_create(jxs_model* model, int n, const int32_t* parent_link, const double* L_H_F, jxs_frames** out) {
   if (out == nullptr) return fail(JXS_EINVAL, "null out");
@@ -951,7 +994,7 @@ int jxs_frames_create(jxs_model* model, int n, const int32_t* parent_link, const
   if (n < 1 || n > JXS_FRAME_MAX_TARGETS)
     return fail(JXS_EINVAL, "number of frame targets " + std::to_string(n) + " outside [1, " + std::to_string(JXS_FRAME_MAX_TARGETS) + "]");
   if (parent_link == nullptr || L_H_F == nullptr) return fail(JXS_EINVAL, "null parent_link or L_H_F");
-  auto make = [&](auto* mt) -> int {
+  return with_typed(model, [&](auto* mt) -> int {
     using T = typename std::remove_pointer_t<decltype(mt)>::value_type;
     const auto& pk = mt->pk;
     const int nL = pk.P.nL;
@@ -987,8 +1030,7 @@ int jxs_frames_create(jxs_model* model, int n, const int32_t* parent_link, const
     }
     *out = f.release();
     return JXS_OK;
-  };
-  return model->dtype == JXS_F64 ? make(model->f64.get()) : make(model->f32.get());
+  });
 }
 int jxs_frames_destroy(jxs_frames* frames) {
   if (frames == nullptr) return JXS_OK;
@@ -1007,30 +1049,21 @@ int jxs_frame_kinematics(jxs_model* model, const jxs_frames* frames, const void*
   if (out_record == nullptr) return fail(JXS_EINVAL, "null out_record");
   if (N <= 0) return fail(JXS_EINVAL, "N must be positive");
   if (in_repr < 0 || in_repr > 2 || out_repr < 0 || out_repr > 2) return fail(JXS_EINVAL, "invalid velocity representation");
-  auto go = [&](auto* mt) -> int {
-    using T = typename std::remove_pointer_t<decltype(mt)>::value_type;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    jxs::KArgs<T> a = mt->args(N);
-    a.state_in = static_cast<const T*>(state);
-    a.out_H = static_cast<T*>(out_record);
-    a.out_a = static_cast<T*>(out_J);
-    a.tgt = static_cast<const T*>(frames->tgt);
-    a.n_tgt = frames->n;
-    a.in_repr = in_repr;
-    a.out_repr = out_repr;
-    a.n_steps = 1;
-    const int mode = jxs::MODE_FRAMES;
-    hipError_t e = mt->spec_launch[mode] != nullptr ? static_cast<hipError_t>(mt->spec_launch[mode](&mt->pk.P, mt->mblk, &a, s))
-                                                    : launch_mode<T>(mode, mt->pk.G, mt->pk.P, mt->mblk, a, s);
-    if (e != hipSuccess) return hip_fail(e, "kernel launch");
-    return JXS_OK;
-  };
-  return model->dtype == JXS_F64 ? go(model->f64.get()) : go(model->f32.get());
+  Launch L = request(jxs::MODE_FRAMES, state, N);
+  L.out_H = out_record;
+  L.out_a = out_J;
+  L.tgt = frames->tgt;
+  L.n_tgt = frames->n;
+  L.in_repr = in_repr;
+  L.out_repr = out_repr;
+  return run(model, L, stream);
 }
 int jxs_refresh_kinematics(jxs_model* model, const void* state, void* out_link_transforms, void* out_link_velocities,
                            int N, void* stream) {
-  return run_any(model, jxs::MODE_KIN, state, nullptr, nullptr, nullptr, 0, nullptr, nullptr, out_link_transforms,
-                 out_link_velocities, N, 1, stream);
+  Launch L = request(jxs::MODE_KIN, state, N);
+  L.out_H = out_link_transforms;
+  L.out_V = out_link_velocities;
+  return run(model, L, stream);
 }
 
 int jxs_comm_unique_id(char id[128]) {

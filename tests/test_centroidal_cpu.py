@@ -3,14 +3,14 @@
 1. The reference's definitions as restated in tests/centroidal_ref.py (oracle CRBA + cached kinematics + the
    reference's adjoints) against an independent statement from the URDF text (tests/maxcoord.py's parser: plain sums
    over the massive URDF bodies), fp64 1e-12; the sign of the reference's potential energy.
-2. The kernel core of MODE_CENTROIDAL (host emulation, tests/emul/jxs_emul_centroidal.cpp) against the restatement,
+2. The kernel core of MODE_CENTROIDAL (host emulation, tests/emul/jxs_emul_query.cpp) against the restatement,
    fp64 1e-10 and fp32, on the zoo, a fixed base with a stored base velocity, a model without joints and a base 1 km
    from the origin -- with the harness's check that the mode touches no LDS and writes every output entry.
 """
 import numpy as np
 import pytest
 
-import centroidal_emul
+import query_emul
 import centroidal_ref as cr
 import helpers
 import jaxsim_amd as ja
@@ -94,7 +94,7 @@ def test_potential_energy_has_the_reference_sign():
 
 def emulate(model, d, dtype):
     block = helpers.odata_to_block(model, d, dtype=dtype)
-    rec, J = centroidal_emul.run(model, block, jacobian=True, dtype=dtype)
+    rec, J = query_emul.run_centroidal(model, block, jacobian=True, dtype=dtype)
     assert np.all(np.isfinite(rec)) and np.all(np.isfinite(J))  # every entry written (the outputs start as NaN)
     N, n = d.base_position.shape[0], model.dofs()
     return rec.T.astype(np.float64), J.T.astype(np.float64).reshape(N, 6, 6 + n)
@@ -169,7 +169,7 @@ def test_record_only_launch_leaves_the_jacobian_alone():
     _, model = model_of("anymal")
     d = cr.random_data(model, 3, seed=9)
     block = helpers.odata_to_block(model, d)
-    rec, J = centroidal_emul.run(model, block, jacobian=False)
+    rec, J = query_emul.run_centroidal(model, block, jacobian=False)
     assert J is None and np.all(np.isfinite(rec))
 
 

@@ -3,7 +3,7 @@
 1. The restatement of tests/coriolis_ref.py pinned without the reference, fp64, in the three representations: ``C nu``
    equals ``h - g`` of the oracle, ``Mdot - 2C`` is skew-symmetric with ``Mdot`` a central difference of the oracle's
    mass matrix along ``qdot``; its ``L_Jdot_WL_B`` equals the oracle's Inertial derivative moved to Body.
-2. The kernel core of MODE_CORIOLIS (host emulation, tests/emul/jxs_emul_coriolis.cpp) against the restatement: fp64 at
+2. The kernel core of MODE_CORIOLIS (host emulation, tests/emul/jxs_emul_query.cpp) against the restatement: fp64 at
    1e-11, fp32 per-model gates; the mass matrix of the same launch against the oracle's; the host conversion of
    ``api/model.py`` to Body and Inertial.  The outputs start as NaN: an entry the kernel does not write must be a
    structural zero.
@@ -16,7 +16,7 @@ import numpy as np
 import pytest
 
 import centroidal_ref as cr
-import coriolis_emul
+import query_emul
 import coriolis_ref as cref
 import helpers
 import jaxsim_amd as ja
@@ -106,8 +106,8 @@ def test_restatement_jacobian_derivative_equals_the_oracle_inertial_one_moved_to
 
 def emulate(model, d, dtype):
     block = helpers.odata_to_block(model, d, dtype=dtype)
-    Cn, Mn = coriolis_emul.run(model, block, dtype=dtype)  # NaN where the kernel does not write
-    C0, M0 = coriolis_emul.run(model, block, fill=0.0, dtype=dtype)  # what jxs_coriolis hands the kernel
+    Cn, Mn = query_emul.run_coriolis(model, block, dtype=dtype)  # NaN where the kernel does not write
+    C0, M0 = query_emul.run_coriolis(model, block, fill=0.0, dtype=dtype)  # what jxs_coriolis hands the kernel
     np.testing.assert_array_equal(np.nan_to_num(Cn), C0)
     np.testing.assert_array_equal(np.nan_to_num(Mn), M0)
     return Cn, C0, M0

@@ -5,7 +5,7 @@
    link, and to the maximal-coordinate solver of tests/maxcoord.py (from the URDF text) on the models of
    tests/test_maxcoord_independent.py at that file's tolerance.  Models whose base link has a pose offset get no link
    wrenches in the comparison with ABA: the reference's two paths differ there (tests/fd_crb_ref.py), which a test states.
-2. The kernel core of MODE_FD_CRB (host emulation, tests/emul/jxs_emul_fd_crb.cpp) against the restatement, with and
+2. The kernel core of MODE_FD_CRB (host emulation, tests/emul/jxs_emul_query.cpp) against the restatement, with and
    without joint forces / link wrenches, every force representation: fp64 at 1e-10, fp32 per-model gates.
 3. The output starts as NaN: every entry is finite afterwards; a fixed base returns six exact zeros.
 4. ``jxs_forward_dynamics_crb`` refuses bad arguments; ``js.model.total_mass``; ``forward_dynamics`` dispatches.
@@ -17,7 +17,7 @@ import numpy as np
 import pytest
 
 import centroidal_ref as cr
-import fd_crb_emul
+import query_emul
 import fd_crb_ref as fref
 import helpers
 import jaxsim_amd as ja
@@ -106,7 +106,7 @@ def emulate(model, d, dtype, tau, f, code):
         kw["tau"] = tau.T
     if f is not None:
         kw.update(link_forces=f.reshape(N, -1).T, force_repr=code)
-    out = fd_crb_emul.run(model, helpers.odata_to_block(model, d, dtype=dtype), dtype=dtype, **kw).T
+    out = query_emul.run_fd_crb(model, helpers.odata_to_block(model, d, dtype=dtype), dtype=dtype, **kw).T
     assert np.all(np.isfinite(out))  # (the output started as NaN)
     return out
 
@@ -166,7 +166,7 @@ def test_every_entry_is_written_and_a_fixed_base_is_exactly_zero(name, dtype):
     model = model_of(name)
     d = cr.random_data(model, 5, seed=4, dtype=dtype)
     tau, f = helpers.random_inputs(model, 5, 5, dtype)
-    out = fd_crb_emul.run(model, helpers.odata_to_block(model, d, dtype=dtype), tau=tau.T, link_forces=f.reshape(5, -1).T,
+    out = query_emul.run_fd_crb(model, helpers.odata_to_block(model, d, dtype=dtype), tau=tau.T, link_forces=f.reshape(5, -1).T,
                           force_repr=2, fill=np.nan, dtype=dtype)  # fmt: skip
     assert out.shape == (6 + model.dofs(), 5) and np.all(np.isfinite(out))
     if not model.floating_base():

@@ -2,7 +2,7 @@
 
 1. The restatement of tests/frames_ref.py pinned without the product: a central finite difference in time of
    ``O_v_WF(q(t))`` at constant ``I_nu`` (closed-form base motion for each representation) equals its ``O_Jdot_WF_I I_nu``.
-2. The kernel core of MODE_FRAMES (host emulation, tests/emul/jxs_emul_frames.cpp) against the restatement for all nine
+2. The kernel core of MODE_FRAMES (host emulation, tests/emul/jxs_emul_query.cpp) against the restatement for all nine
    (input, output) representation pairs, with and without the Jacobian, fp64 1e-10 and fp32 per-model gates; links and
    model frames; a fixed base with a stored base velocity, a base-link offset, a base a kilometre from the origin.  The
    outputs start as NaN, so an entry the kernel does not write fails.
@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 
 import centroidal_ref as cr
-import frames_emul
+import query_emul
 import frames_ref as fr
 import helpers
 import jaxsim_amd as ja
@@ -60,7 +60,7 @@ def targets(model, which):
 def check(model, d, d_ref, which, I, O, tol, jacobian=True, dtype=np.float64):
     P, H = targets(model, which)
     block = helpers.odata_to_block(model, d, dtype=dtype)
-    rec, J = frames_emul.run(model, block, P, H, I, O, jacobian=jacobian, dtype=dtype)
+    rec, J = query_emul.run_frames(model, block, P, H, I, O, jacobian=jacobian, dtype=dtype)
     assert np.all(np.isfinite(rec)) and (J is None or np.all(np.isfinite(J)))  # every entry written
     ref = fr.restate(model, with_rep(model, d_ref, I), P, H, I, O)
     Hk = np.zeros(ref["H"].shape)
@@ -121,8 +121,8 @@ def test_fixed_base_bias_includes_the_stored_base_velocity():
     d1 = cr.random_data(model, 2, seed=8)
     d0 = cr.random_data(model, 2, seed=8, base_velocity=False)
     P, H = fr.link_targets(model)
-    r1, _ = frames_emul.run(model, helpers.odata_to_block(model, d1), P, H, 2, 2, jacobian=False)
-    r0, _ = frames_emul.run(model, helpers.odata_to_block(model, d0), P, H, 2, 2, jacobian=False)
+    r1, _ = query_emul.run_frames(model, helpers.odata_to_block(model, d1), P, H, 2, 2, jacobian=False)
+    r0, _ = query_emul.run_frames(model, helpers.odata_to_block(model, d0), P, H, 2, 2, jacobian=False)
     assert np.abs(r1[..., 18:] - r0[..., 18:]).max() > 1e-3
 
 
