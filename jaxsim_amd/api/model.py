@@ -362,7 +362,17 @@ def forward_dynamics_crb(model: JaxSimModel, data: JaxSimModelData, *, joint_for
     acceleration with the link wrenches applied, the tree-sparse ``L^T D L`` factorisation of ``M``.  Same return
     convention as ``forward_dynamics_aba``.  Like the reference's CRB path the link wrenches act through the link
     Jacobians: for a model whose base link has a pose offset that differs from ``forward_dynamics_aba`` when
-    ``link_forces`` are given in Body or Mixed representation."""
+    ``link_forces`` are given in Body or Mixed representation.
+
+    float32: ``M`` is ill-conditioned in joint coordinates on long serial chains (condition number 1e6 for 64 links), and
+    a float32 factorisation of it -- this kernel's as much as ``numpy.linalg.solve`` on the reference's float32 ``M`` --
+    loses up to 1e-2 of the largest acceleration there.  The float32 kernel therefore corrects its solution with one
+    residual step (a second RNEA pass with the solution, the factor reused).  Measured worst error against the float64
+    restatement over 323 random trees (host emulation of the kernel, ``profiles/query_modes_fuzz_campaign.txt``), floating
+    serial chains by length: up to 48 links 6e-6, 49 .. 56 links 6.5e-5, 57 .. 64 links 3.0e-4 (the reference's
+    formulation in float32 on the same states: 4e-4, 1.1e-3, 1.0e-2; without the residual step 1.6e-3, 4.7e-3, 1.3e-2).
+    The articulated-body path measures about the same on such chains (2e-4 on 64 links) and is the faster kernel: for long
+    serial chains in float32 ``forward_dynamics(..., prefer_aba=True)`` remains the one to use."""
     return _forward_dynamics_device(model, data, "jxs_forward_dynamics_crb", joint_forces, link_forces)
 
 

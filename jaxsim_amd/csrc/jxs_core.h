@@ -2613,27 +2613,35 @@ struct Core {
     const V zero = V(T(0));
     const VI jrow_c = vsel(jrow >= 0, jrow, lane * 0);
     const V sdd = (A.in_a != nullptr) ? vsel(is_joint, ln.gload(A.in_a, jrow_c + 6, 6 + P.n), zero) : zero;
-    // base acceleration in C: a_0 = (Wdot_v - W_g) moved to the C origin (floating) or -W_g
-    V al[3], aa[3];
-    {
-      V wl[3] = {zero, zero, zero}, wa[3] = {zero, zero, zero};
-      if (P.floating && A.in_a != nullptr) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-          wl[k] = ln.gload_u(A.in_a, k, 6 + P.n);
-          wa[k] = ln.gload_u(A.in_a, 3 + k, 6 + P.n);
-        }
-      }
-      V t[3];
-      cross(wa, pB, t);  // a_lin^C = a_lin^W + wdot x p_B
+    // base acceleration in C: a_0 = Wdot_v moved to the C origin (floating) or zero
+    V wl[3] = {zero, zero, zero}, wa[3] = {zero, zero, zero};
+    if (P.floating && A.in_a != nullptr) {
 #pragma unroll
       for (int k = 0; k < 3; ++k) {
-        const V base_l = wl[k] + t[k], base_a = wa[k];
-        al[k] = vsel(is_root, base_l, Sl[k] * sdd + cl[k]);
-        aa[k] = vsel(is_root, base_a, Sa[k] * sdd + ca[k]);
+        wl[k] = ln.gload_u(A.in_a, k, 6 + P.n);
+        wa[k] = ln.gload_u(A.in_a, 3 + k, 6 + P.n);
       }
-      al[2] = al[2] - vsel(is_root, V(P.g), zero);
     }
+    V t[3], bl0[3];
+    cross(wa, pB, t);  // a_lin^C = a_lin^W + wdot x p_B
+#pragma unroll
+    for (int k = 0; k < 3; ++k) bl0[k] = wl[k] + t[k];
+    rnea_sweeps_of(level, jump, child, is_root, Sl, Sa, cl, ca, mass, cw, Ic, bl, ba, fl, fa, sdd, bl0, wa, tq, f6);
+  }
+  // The same for accelerations held in registers: `sdd` of this lane's joint (zero in the lanes without one), `a0l` / `a0a`
+  // = the acceleration of the base in C (wave-uniform; gravity is added here).  fd_crb() calls it a second time, with its
+  // own solution, for the residual.
+  JXS_HD void rnea_sweeps_of(const VI& level, const VI* jump, const VI* child, const VM& is_root, const V* Sl, const V* Sa,
+                             const V* cl, const V* ca, const V& mass, const V* cw, const V* Ic, const V* bl, const V* ba,
+                             const V* fl, const V* fa, const V& sdd, const V* a0l, const V* a0a, V& tq, V* f6) const {
+    const V zero = V(T(0));
+    V al[3], aa[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      al[k] = vsel(is_root, a0l[k], Sl[k] * sdd + cl[k]);
+      aa[k] = vsel(is_root, a0a[k], Sa[k] * sdd + ca[k]);
+    }
+    al[2] = al[2] - vsel(is_root, V(P.g), zero);  // (a_0 - W_g)
     prefix6(jump, al, aa);  // a_i = a_lambda + S sdd + v x vJ  (rnea.py:150-152)
     // f_i = M a + v x* M v - f_ext  (rnea.py:163-168)
     {
@@ -3224,10 +3232,11 @@ struct Core {
     ln.stamp(A, 9);  // factorisation
     // ---- base block
     V x0[6] = {zero, zero, zero, zero, zero, zero};
-    if (P.floating) {
-      V MA0[21], p0[6], a6[6];
+    V MA0[21];
 #pragma unroll
-      for (int e = 0; e < 21; ++e) MA0[e] = Ic[e] - E[e];
+    for (int e = 0; e < 21; ++e) MA0[e] = Ic[e] - E[e];
+    if (P.floating) {
+      V p0[6], a6[6];
 #pragma unroll
       for (int e = 0; e < 6; ++e) p0[e] = f6[e] + e6[e];
       solve6(MA0, p0, a6);  // a_0 = -MA0^-1 p0, meaningful in the base lane only
@@ -3235,21 +3244,67 @@ struct Core {
       for (int e = 0; e < 6; ++e) x0[e] = ln.shfl(a6[e], zl);
       ln.fence();
     }
-    // ---- back-substitution, base to leaves
+    // ---- back-substitution, base to leaves: sdd of the right-hand side column `y` (after its elimination) and the base
+    // acceleration `a0`
     const V invd_own = vsel(is_joint && !(head[7] == zero), vrcp_acc(vsel(head[7] == zero, V(T(1)), head[7])), zero);
-    V acc = head[6];
+    auto back_substitute = [&](const V& y, const V* a0) {
+      V acc = y;
 #pragma unroll
-    for (int e = 0; e < 6; ++e) acc = acc - head[e] * x0[e];
-    for (int i = 1; i < P.nL - 1; ++i) {  // (the last lane has no descendants)
-      const VI src = zl + i;
-      const V xi = ln.shfl(acc * invd_own, src);
-      const VI lvi = ln.shfl(lv1, src), subi = ln.shfl(sub, src);
-      ln.fence();
-      const VM desc = is_joint && (lane > i) && (lane < subi + i);
-      const V hki = ln.lds_read(rowa + 7 + lvi);
-      acc = acc - vsel(desc, hki * xi, zero);
+      for (int e = 0; e < 6; ++e) acc = acc - head[e] * a0[e];
+      for (int i = 1; i < P.nL - 1; ++i) {  // (the last lane has no descendants)
+        const VI src = zl + i;
+        const V xi = ln.shfl(acc * invd_own, src);
+        const VI lvi = ln.shfl(lv1, src), subi = ln.shfl(sub, src);
+        ln.fence();
+        const VM desc = is_joint && (lane > i) && (lane < subi + i);
+        const V hki = ln.lds_read(rowa + 7 + lvi);
+        acc = acc - vsel(desc, hki * xi, zero);
+      }
+      return acc * invd_own;
+    };
+    V sdd = back_substitute(head[6], x0);
+    // ---- fp32: one step of residual correction.  On a long serial chain M is ill-conditioned in joint coordinates
+    // (cond 1e6 for 64 links) and a float32 factorisation of it -- this one as much as numpy.linalg.solve on the
+    // reference's float32 M -- loses up to 1e-2 of the largest acceleration; RNEA does not go through M, so the residual
+    // r = B tau + J^T f - h - M nu_dot of a second pass WITH the solution carries the rounding of a recursion only, and
+    // nu_dot += M^-1 r through the factor that is still in the LDS takes the error of a 64-link chain from 5.1e-3 to 8.9e-5
+    // and the worst of 323 random trees from 1.3e-2 to 3.0e-4 (host emulation, profiles/query_modes_fuzz_campaign.txt).
+    // fp64 is at 3e-11 without it and keeps its instruction stream.
+    if (sizeof(T) == 4) {
+      V tq2, g6[6];
+      rnea_sweeps_of(level, jump, child, is_root, S6, S6 + 3, cl, ca, mass, cw, Ic3, bl, ba, fl, fa, sdd, x0, x0 + 3, tq2, g6);
+      V rb = vsel(is_joint, tau - tq2, zero);
+      V d6[6] = {zero, zero, zero, zero, zero, zero};
+      for (int k = P.nL - 1; k >= 1; --k) {  // y = L^-T r: the elimination above, for this column alone
+        const int rk = k * Ws;
+        const V bk = ln.shfl(rb, zl + k);    // final: every deeper pivot is done
+        ln.fence();
+        V hk[8];
+        ln.template lds_readv<8>(zl + rk, hk);
+        const V hki = ln.lds_read(colm + rk);
+        const V invd = vsel(hk[7] == zero, zero, vrcp_acc(hk[7]));
+        const VM anc = is_joint && (lane < k) && (lane + sub > k);
+        const V s = invd * bk;
+        rb = rb - vsel(anc, hki * s, zero);
+        if (P.floating) {
+#pragma unroll
+          for (int i = 0; i < 6; ++i) d6[i] = d6[i] + hk[i] * s;
+        }
+      }
+      V dx0[6] = {zero, zero, zero, zero, zero, zero};
+      if (P.floating) {
+        V p0[6], a6[6];
+#pragma unroll
+        for (int e = 0; e < 6; ++e) p0[e] = g6[e] + d6[e];
+        solve6(MA0, p0, a6);
+#pragma unroll
+        for (int e = 0; e < 6; ++e) dx0[e] = ln.shfl(a6[e], zl);
+        ln.fence();
+      }
+      sdd = sdd + back_substitute(rb, dx0);
+#pragma unroll
+      for (int e = 0; e < 6; ++e) x0[e] = x0[e] + dx0[e];
     }
-    const V sdd = acc * invd_own;
     V t[3];
     cross(x0 + 3, pB, t);
 #pragma unroll

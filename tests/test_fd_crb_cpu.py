@@ -30,12 +30,17 @@ from oracle import refstep as rs
 from test_coriolis_cpu import TEXTS, model_of
 
 REPS = (VelRepr.Inertial, VelRepr.Body, VelRepr.Mixed)  # index = the force representation code of the kernel
-# fp32: measured worst relative error of the emulation against the fp64 restatement (seed 3, N = 4, the six input
-# combinations below) x 3; measured (MODE_FD_CRB | the emulated MODE_FD, ABA, on the same states and inputs):
+# fp32: the gates are the worst relative error of the emulation against the fp64 restatement (seed 3, N = 4, the six input
+# combinations below) x 3 as measured BEFORE the kernel corrected its fp32 solution with one residual step; measured then
+# (MODE_FD_CRB | the emulated MODE_FD, ABA, on the same states and inputs, against the oracle's ABA):
 # anymal 2.65e-6 | 1.81e-6, icub 4.98e-5 | 1.79e-5, octopod 9.81e-5 | 4.99e-5, cartpole 1.45e-6 | 1.60e-7,
 # chain5 2.74e-6 | 5.04e-7, box 2.05e-7 | 2.05e-7, lumped 6.18e-6 | 2.11e-6, chain9f 6.38e-6 | 2.96e-6
-# (the ABA figures against the oracle's ABA; CRB is nowhere more than 10 x worse: the unanchored composite inertias and
-# the pivots D_i = S_i . Ic_i S_i carry the parallel-axis cancellation that the anchored ABA avoids)
+# -- at most 9 x ABA on these short trees, but 80 .. 110 x on serial chains of 40 .. 64 links (5e-3 .. 1.3e-2 against
+# 4e-5 .. 6e-4, profiles/query_modes_fuzz_campaign.txt): a float32 factorisation of M, whose condition number in joint
+# coordinates reaches 1e6 there (numpy.linalg.solve on the reference's float32 M loses as much).  With the residual step
+# (csrc/jxs_core.h fd_crb) the same cases measure
+# anymal 1.27e-6, icub 1.73e-5, octopod 4.24e-5, cartpole 3.12e-7, chain5 8.07e-7, box 2.01e-7, lumped 6.52e-7, chain9f 9.32e-7
+# and the worst of 323 random trees of up to 64 links 3.0e-4; the gates stay where they were.
 FP32_TOL = {"anymal": 8e-6, "icub": 1.5e-4, "octopod": 2.95e-4, "cartpole": 4.4e-6, "chain5": 8.2e-6, "box": 6.2e-7, "lumped": 1.85e-5,
             "chain9f": 1.9e-5}
 
