@@ -1462,6 +1462,12 @@ struct Core {
   // inherits its parent's slot, so along a chain "propagate to the parent" is a register add in
   // the same lane; only extra children cross slots (one 7-value shuffle batch).  U = MA S is a
   // column all-reduce over the 8 lanes (3 DPP adds per entry, MA symmetric).
+  // 1.0 where bit `b` of a lane-constant word is set, else 0.0: the lane backend's own form where it has one (fp32 on the
+  // device builds the pattern of 1.0f from the bit, DeviceLanes::one_if_bit), the select otherwise
+  template <class LL>
+  static JXS_HD auto bit_factor(const VI& bits, int b, int) -> decltype(LL::one_if_bit(bits, b)) { return LL::one_if_bit(bits, b); }
+  template <class LL>
+  static JXS_HD V bit_factor(const VI& bits, int b, long) { return vsel(((bits >> b) & 1) != 0, V(T(1)), V(T(0))); }
   struct RowTabs {
     VI rec[kRowLevels], ppull[kRowLevels], pull[kRowLevels][kRowExtra], fcbits;
   };
@@ -1634,7 +1640,7 @@ struct Core {
             }
             // what a first child hands to its parent in the same lanes: x 1, else x 0 (values are finite: packed multiplies
             // instead of seven selects)
-            const V fcf = vsel(((rt.fcbits >> Lv) & 1) != 0, V(T(1)), zero);
+            const V fcf = bit_factor<L>(rt.fcbits, Lv, 0);
             if (!L::scale6_packed(Ma, fcf, accM)) {
 #pragma unroll
               for (int j = 0; j < 6; ++j) accM[j] = Ma[j] * fcf;

@@ -522,6 +522,26 @@ struct DeviceLanes {
     }
   }
 
+  // 1.0 where bit `b` (a compile-time constant after unrolling) of the lane-constant word `bits` is set, else 0.0 -- the
+  // factor a packed multiply applies where a select per value stood.  fp32: the sign-extended bit ANDed with the pattern of
+  // 1.0f, two integer instructions where bit test, compare and select took three; exact (the two values are 0.0f and 1.0f)
+  static __device__ __forceinline__ V one_if_bit(int bits, int b) {
+    if constexpr (sizeof(T) == 4) {
+      return __int_as_float(__builtin_amdgcn_sbfe(bits, b, 1) & 0x3f800000);
+    } else {
+      return ((bits >> b) & 1) != 0 ? T(1) : T(0);
+    }
+  }
+  // x + x@(the lane CTRL names): ONE v_add_f32_dpp, written so that the compiler sees it.  The update_dpp that feeds a single
+  // addition is folded into the addition's DPP operand, the compiler pads the VALU-write -> DPP-read hazard itself -- with
+  // whatever independent instruction it finds, an s_nop only where there is none -- and the empty asm keeps the multiply
+  // that produced x apart from this addition (contracted into an fma, the sum would round differently and the v_mov_dpp
+  // would stay).  The hand-written blocks this replaces carried fixed s_nop 1 / s_nop 0 in every stage.
+  template <int CTRL>
+  static __device__ __forceinline__ float add_dpp(float x) {
+    asm("" : "+v"(x));
+    return x + dpp<CTRL>(x);
+  }
   // sum over the 8 lanes of a slot (row-distributed ABA), result in all 8: three DPP adds
   __device__ __forceinline__ double allreduce8(double x) const {
     x = x + dpp<0xB1>(x);   // quad_perm:[1,0,3,2]
@@ -529,16 +549,12 @@ struct DeviceLanes {
     x = x + dpp<0x141>(x);  // row_half_mirror
     return x;
   }
-  // fp32: three v_add_f32_dpp written out -- the compiler turns the first stage into v_mov_dpp + v_fmac (recomputing the
-  // product that feeds it), one dependent instruction more on the base-to-leaves chain of pass 3
+  // fp32: three v_add_f32_dpp (add_dpp) -- left to itself the compiler turns the first stage into v_mov_dpp + v_fmac
+  // (recomputing the product that feeds it), one dependent instruction more on the base-to-leaves chain of pass 3
   __device__ __forceinline__ float allreduce8(float x) const {
-    asm volatile("s_nop 1\n\t"
-                 "v_add_f32_dpp %0, %0, %0 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-                 "s_nop 1\n\t"
-                 "v_add_f32_dpp %0, %0, %0 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-                 "s_nop 1\n\t"
-                 "v_add_f32_dpp %0, %0, %0 row_half_mirror row_mask:0xf bank_mask:0xf bound_ctrl:1"
-                 : "+&v"(x));
+    x = add_dpp<0xB1>(x);   // quad_perm:[1,0,3,2]
+    x = add_dpp<0x4E>(x);   // quad_perm:[2,3,0,1]
+    x = add_dpp<0x141>(x);  // row_half_mirror
     return x;
   }
   // seven independent 8-lane reductions advanced stage by stage: consecutive DPP instructions never read a
@@ -560,15 +576,13 @@ struct DeviceLanes {
                  : "+&v"(x[0]), "+&v"(x[1]), "+&v"(x[2]), "+&v"(x[3]), "+&v"(x[4]), "+&v"(x[5]), "+&v"(x[6]));
 #undef JXS_DPP7
   }
-  // two independent 8-lane reductions, stage by stage (d = S.U and S.pA of a tree level)
+  // two independent 8-lane reductions, stage by stage (d = S.U and S.pA of a tree level).  Each stage reads what its
+  // predecessor wrote one instruction earlier: the compiler fills that wait state, and the two in front of the first
+  // stage, with the level's integer work (record addresses, table unpacking) where the asm block held three s_nop
   __device__ __forceinline__ void allreduce8x2(float* x) const {
-#define JXS_DPP2(CTRL)                                                              \
-  "v_add_f32_dpp %0, %0, %0 " CTRL " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t" \
-  "v_add_f32_dpp %1, %1, %1 " CTRL " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-    // (two values: each stage reads what its predecessor wrote one instruction earlier -- one wait state more)
-    asm volatile("s_nop 1\n\t" JXS_DPP2("quad_perm:[1,0,3,2]") "s_nop 0\n\t" JXS_DPP2("quad_perm:[2,3,0,1]") "s_nop 0\n\t" JXS_DPP2("row_half_mirror")
-                 : "+&v"(x[0]), "+&v"(x[1]));
-#undef JXS_DPP2
+    x[0] = add_dpp<0xB1>(x[0]), x[1] = add_dpp<0xB1>(x[1]);    // quad_perm:[1,0,3,2]
+    x[0] = add_dpp<0x4E>(x[0]), x[1] = add_dpp<0x4E>(x[1]);    // quad_perm:[2,3,0,1]
+    x[0] = add_dpp<0x141>(x[0]), x[1] = add_dpp<0x141>(x[1]);  // row_half_mirror
   }
   __device__ __forceinline__ void allreduce8x2(double* x) const {
     x[0] = allreduce8(x[0]), x[1] = allreduce8(x[1]);

@@ -16,6 +16,13 @@ every piece, and prints it beside the measured cycles: from a log of tools/phase
 here when a device is present.
 
   JAXSIM_AMD_SPEC_EXTRA_FLAGS=-DJXS_PHASE_TIMING python tools/issue_floor.py [--measured gpurun_out/.../phases_1024.log]
+
+--production prices the object that ships instead (no JXS_PHASE_TIMING, so no stamps): the whole kernel as one piece, by
+instruction class, with the floating-point instructions apart from the glue around them (integer / address / compare
+VALU, selects, moves, nops, waits and scalar instructions).  No GPU is needed; JAXSIM_AMD_SPEC_CSRC=<dir> prices the kernel
+of another copy of the sources with the same table (an earlier commit, for a before / after comparison):
+
+  python tools/issue_floor.py --production [--measured-ticks 13718]
 """
 import argparse
 import collections
@@ -26,12 +33,14 @@ import sys
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-os.environ.setdefault("JAXSIM_AMD_SPEC_EXTRA_FLAGS", "-DJXS_PHASE_TIMING")
+if "--production" not in sys.argv:
+    os.environ.setdefault("JAXSIM_AMD_SPEC_EXTRA_FLAGS", "-DJXS_PHASE_TIMING")
 import bench  # noqa: E402
 from jaxsim_amd import isa_lint, specialize  # noqa: E402
 
 # ticks one more instruction of the class costs a wave that is alone on its SIMD (profiles/r05_issue_rate_ubench.txt)
-COST = {"valu": 5.35, "cndmask": 6.44, "pk": 4.05, "dpp": 4.10, "trans": 7.12, "vmov": 3.20, "salu": 3.30, "snop": 3.14,
+# (s_nop 1 -- two wait states -- has a row of its own there: 9.49, three times an s_nop 0)
+COST = {"valu": 5.35, "cndmask": 6.44, "pk": 4.05, "dpp": 4.10, "trans": 7.12, "vmov": 3.20, "salu": 3.30, "snop": 3.14, "snop1": 9.49,
         "waitcnt": 4.46, "branch": 17.17, "bperm": 18.42, "ds_read": 14.9, "ds_write": 14.9, "vmem": 16.0, "smem": 3.30}
 TRANS = ("v_rcp", "v_rsq", "v_sqrt", "v_sin", "v_cos", "v_exp", "v_log")
 PHASES = {1: "loads arrive", 2: "actuation+local xform", 3: "FK (pointer jumping)", 4: "velocities", 5: "contacts", 6: "inertia+bias",
@@ -41,7 +50,7 @@ PHASES = {1: "loads arrive", 2: "actuation+local xform", 3: "FK (pointer jumping
 def classify(i) -> str:
     op = i.op
     if op == "s_nop":
-        return "snop"
+        return "snop" if i.args[:1] in ([], ["0"]) else "snop1"
     if op == "s_waitcnt":
         return "waitcnt"
     if op.startswith("s_cbranch") or op == "s_branch":
@@ -71,6 +80,52 @@ def classify(i) -> str:
             return "vmov"
         return "valu"
     return "salu"
+
+
+def is_fp(i) -> bool:
+    """A floating-point instruction (arithmetic, DPP or packed or not, transcendental, conversion, compare)."""
+    return i.op.startswith("v_") and re.search(r"_f(16|32|64)", i.op) is not None
+
+
+def production_table(insts, measured=None):
+    """The kernel as one piece: instructions and priced ticks by class, floating point apart from the glue."""
+    end = max(k for k, i in enumerate(insts) if i.op == "s_endpgm")  # (behind the last s_endpgm: the padding of the code object)
+    insts = insts[: end + 1]
+    # the kernel-argument preload header (s_load .. s_branch and s_nop 0 up to 256 bytes) is skipped by the hardware when
+    # the arguments arrive preloaded, which is how the launcher calls the kernel: not part of the wave's stream
+    b = next((k for k, i in enumerate(insts[:16]) if i.op == "s_branch"), None)
+    if b is not None and all(i.op.startswith(("s_load", "s_waitcnt")) for i in insts[:b]):
+        k = b + 1
+        while k < len(insts) and insts[k].op == "s_nop":
+            k += 1
+        insts = insts[k:]
+    groups = [("fp arithmetic (plain, DPP, packed, transcendental, compare)", lambda i, c: is_fp(i)),
+              ("LDS (bpermute, reads, writes)", lambda i, c: c in ("bperm", "ds_read", "ds_write")),
+              ("integer / address / compare VALU", lambda i, c: c in ("valu", "dpp", "pk", "trans")),
+              ("v_cndmask", lambda i, c: c == "cndmask"),
+              ("s_nop", lambda i, c: c in ("snop", "snop1")),
+              ("v_mov_b32 (plain and DPP), v_accvgpr", lambda i, c: c == "vmov" or i.op.startswith("v_mov")),
+              ("s_waitcnt, SALU, branches", lambda i, c: c in ("waitcnt", "salu", "branch")),
+              ("vector memory, scalar loads", lambda i, c: c in ("vmem", "smem"))]
+    rows = [[name, 0, 0.0] for name, _ in groups]
+    per_class = collections.Counter()
+    for i in insts:
+        c = classify(i)
+        per_class[c] += 1
+        for row, (_, pred) in zip(rows, groups):
+            if pred(i, c):
+                row[1] += 1
+                row[2] += COST[c]
+                break
+        else:
+            raise SystemExit("unclassified: " + i.text)
+    total = sum(r[2] for r in rows)
+    print(f"| {'class':62s} | instructions | ticks | share |\n|---|---|---|---|")
+    for name, n, t in rows:
+        print(f"| {name:62s} | {n:5d} | {t:6.0f} | {100 * t / total:4.1f} % |")
+    print(f"| {'total':62s} | {len(insts):5d} | {total:6.0f} |" + (f" measured {measured:.0f}: measured / priced = {measured / total:.3f} |" if measured else " |"))
+    print("by cost class: " + " ".join(f"{k}={per_class[k]}" for k in COST if per_class[k]))
+    return total
 
 
 def segments(insts):
@@ -122,6 +177,8 @@ def main():
     ap.add_argument("--measured", help="a log of tools/phase_timing.py (same kernel, same flags)")
     ap.add_argument("--model", default="icub23", help="icub23 (the headline) | quadruped_rigid (BASELINE config 5: the stage loop is unrolled, the stamps of stage 0 and of the impact stage follow each other)")
     ap.add_argument("--dump", action="store_true", help="print the instructions of every piece")
+    ap.add_argument("--production", action="store_true", help="price the shipped object (no stamps) as one piece, by class")
+    ap.add_argument("--measured-ticks", type=float, help="--production: the measured length of the kernel, for the ratio measured / priced")
     args = ap.parse_args()
     model = bench.build_quadruped_rigid() if args.model == "quadruped_rigid" else bench.build_model(args.model)
     path = specialize.compile(model, np.float32, specialize.mode_of(model))
@@ -132,6 +189,10 @@ def main():
                 insts = ii
     if insts is None:
         raise SystemExit("no step kernel in " + str(path))
+    if args.production:
+        print(f"{path.name}: sources {specialize.source_sha()}; issue cost per class (ticks): " + " ".join(f"{k}={v}" for k, v in COST.items()))
+        production_table(insts, args.measured_ticks)
+        return
     if not any(i.op == "s_memtime" for i in insts):
         raise SystemExit("the object carries no stamps: set JAXSIM_AMD_SPEC_EXTRA_FLAGS=-DJXS_PHASE_TIMING")
     meas = measured_from_log(args.measured) if args.measured else {}

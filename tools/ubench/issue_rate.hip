@@ -63,6 +63,12 @@ __global__ void kx(float* out, long long* t, int slot, int stride = 16) {
     if (KIND == 17) BODY("ds_read_b32 %0, %8\ns_waitcnt lgkmcnt(0)\n");
     if (KIND == 18) BODY("ds_read_b128 %3, %8\ns_waitcnt lgkmcnt(0)\n");
     if (KIND == 19) BODY("ds_bpermute_b32 %0, %8, %0\nds_bpermute_b32 %1, %8, %1\nds_bpermute_b32 %5, %8, %5\ns_waitcnt lgkmcnt(0)\n");
+    // two wait states in front of a DPP that reads the v_fma's result: one s_nop 1, two s_nop 0, or two independent v_mov
+#define DPPA "v_add_f32_dpp %0, %0, %0 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf bound_ctrl:1\n"
+    if (KIND == 20) BODY("s_nop 0\ns_nop 0\n");
+    if (KIND == 21) BODY("s_nop 1\n" DPPA);
+    if (KIND == 22) BODY("s_nop 0\ns_nop 0\n" DPPA);
+    if (KIND == 23) BODY("v_mov_b32 %1, %6\nv_mov_b32 %5, %6\n" DPPA);
   }
   __builtin_amdgcn_sched_barrier(0);
   long long t1 = __builtin_readcyclecounter();
@@ -83,7 +89,7 @@ int main() {
   }
   for (int rep = 0; rep < 2; ++rep) {
 #define L(K) hipLaunchKernelGGL(kx<K>, dim3(1), dim3(64), 0, 0, d, t, 8 + K);
-    L(0) L(1) L(2) L(3) L(4) L(5) L(6) L(7) L(8) L(9) L(10) L(11) L(12) L(13) L(14) L(15) L(16) L(17) L(18) L(19)
+    L(0) L(1) L(2) L(3) L(4) L(5) L(6) L(7) L(8) L(9) L(10) L(11) L(12) L(13) L(14) L(15) L(16) L(17) L(18) L(19) L(20) L(21) L(22) L(23)
   }
   const int strides[] = {16, 32, 48, 64, 80, 84, 96, 128};
   for (int rep = 0; rep < 2; ++rep)
@@ -99,10 +105,11 @@ int main() {
   const char* names[] = {"(v_fma_f32 alone)", "s_nop 0", "s_waitcnt (satisfied)", "s_add_u32", "v_cndmask_b32", "v_pk_fma_f32", "v_add_f32 dpp",
                          "v_rcp_f32", "ds_bpermute_b32 (16 in flight)", "ds_read_b32 (16 in flight)", "ds_read_b128 (16 in flight)", "s_cmp + s_cbranch (not taken)",
                          "s_nop 1", "v_mov_b32", "ds_bpermute + wait (dependent)", "ds_write_b32 + ds_read_b32 + wait", "ds_write_b128 + ds_read_b128 + wait",
-                         "ds_read_b32 + wait", "ds_read_b128 + wait", "3 x ds_bpermute + wait"};
+                         "ds_read_b32 + wait", "ds_read_b128 + wait", "3 x ds_bpermute + wait", "2 x s_nop 0", "s_nop 1 + dependent v_add_f32 dpp",
+                         "2 x s_nop 0 + dependent v_add_f32 dpp", "2 x v_mov_b32 + dependent v_add_f32 dpp"};
   const double base = (double)h[8] / 2048.0;
   printf("dependent v_fma_f32: %.2f ticks each\n", base);
-  for (int kx_ = 1; kx_ < 20; ++kx_) printf("  + %-32s %6.2f ticks\n", names[kx_], (double)h[8 + kx_] / 2048.0 - base);
+  for (int kx_ = 1; kx_ < 24; ++kx_) printf("  + %-32s %6.2f ticks\n", names[kx_], (double)h[8 + kx_] / 2048.0 - base);
   for (int i = 0; i < 8; ++i)
     printf("lane stride %3d B: ds_write_b128 + ds_read_b128 + wait %6.2f ticks, ds_read_b128 (16 in flight) %6.2f ticks\n", strides[i],
            (double)h[32 + i] / 2048.0 - base, (double)h[40 + i] / 2048.0 - base);
