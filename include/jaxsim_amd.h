@@ -275,6 +275,40 @@ int jxs_tile_to_env_major(const void* src, void* dst, int rows, int N, int tile,
  * not normalised (jnp.allclose(q.q, 1)), [2] = environments with any non-finite state entry.      */
 int jxs_validate_state(jxs_model* model, const void* state, int N, int* counts3, void* stream);
 
+/* ---- the episode loop around `step`: reset, pick and flag environments on the device ----------------
+ * All three work on the tiled storage [ceil(N / tile)][rows][tile] of any batched argument, are asynchronous on
+ * `stream` and neither allocate, synchronise nor read anything on the host: they can sit between two jxs_step
+ * launches of a stream in flight.  `dtype` is JXS_F32 or JXS_F64; words are copied as bits.
+ *
+ * jxs_env_select: out[:, e] = mask[e] ? a[:, e] : b[:, e] for every environment e < N -- the reference's
+ *   `jax.tree.map(lambda x, y: jnp.where(done, x, y), fresh, data)` under vmap.  `mask` = N bytes on the device in
+ *   environment order, any non-zero byte is true (what a bool array of another framework holds); it is never read
+ *   at or beyond N.  The padding columns of the last tile take b's words.  out == b (in-place reset), out == a and
+ *   a == b are allowed; any other overlap is not.  In place, a tile whose mask bytes are all zero costs the read
+ *   of those bytes only.                                                                                        */
+int jxs_env_select(const uint8_t* mask, const void* a, const void* b, void* out, int rows, int N, int tile, int dtype,
+                   void* stream);
+
+/* jxs_env_copy: for k < K, environment src_idx[k] of `src` (src_N environments, tiling src_tile) is copied to
+ *   environment dst_idx[k] of `dst` (dst_N, dst_tile); a null index array means k itself.  A tiling of 1 IS the
+ *   environment-major layout [N][rows], so this one call is the reference's `jax.tree.map(lambda x: x[idx], data)`
+ *   (gather into a smaller batch), `x.at[idx].set(y)` (scatter fresh states into a running batch) and both
+ *   directions of an exchange with another framework's (K, rows) tensor.  The index arrays live on the device:
+ *   every index is checked against src_N / dst_N in the kernel and an entry with either index out of range is
+ *   skipped entirely -- nothing outside the two blocks is read or written.  Duplicate destinations leave that one
+ *   environment unspecified (one of the sources, or a mixture of their rows) and affect nothing else.  `src` and
+ *   `dst` must not overlap.                                                                                      */
+int jxs_env_copy(const void* src, int src_N, int src_tile, const int32_t* src_idx, void* dst, int dst_N, int dst_tile,
+                 const int32_t* dst_idx, int rows, int K, int dtype, void* stream);
+
+/* jxs_env_flags: one byte per environment into `out_flags` (N bytes on the device), the per-environment form of
+ *   jxs_validate_state -- the reference's `jnp.isfinite(x).all()` per vmapped instance, without a download:
+ *   bit 0 (JXS_ENV_NONFINITE): some word of the environment is NaN or infinite (the rule of counts3[2]);
+ *   bit 1 (JXS_ENV_QUAT_NOT_UNIT): the quaternion holds no NaN and is not of unit norm (the rule of counts3[1]).
+ *   A NaN quaternion sets bit 0 only.  The bytes can be handed to jxs_env_select as its mask.                */
+enum { JXS_ENV_NONFINITE = 1, JXS_ENV_QUAT_NOT_UNIT = 2 };
+int jxs_env_flags(jxs_model* model, const void* state, int N, uint8_t* out_flags, void* stream);
+
 /* RigidContacts only.  A contact-force QP or an impact solve whose result is not finite (fp32 on a numerically
  * singular stance) is DISCARDED -- that environment takes the step without contact forces / without the
  * velocity reset instead of poisoning its state -- where the reference would propagate NaN

@@ -239,6 +239,9 @@ def _declare(lib):
         "jxs_tile_from_env_major": [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp],
         "jxs_tile_to_env_major": [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp],
         "jxs_validate_state": [vp, vp, C.c_int, C.POINTER(C.c_int), vp],
+        "jxs_env_select": [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp],
+        "jxs_env_copy": [vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp],
+        "jxs_env_flags": [vp, vp, C.c_int, vp, vp],
         "jxs_step_repeat": [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp],
         "jxs_step_repeat_timed": [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, C.POINTER(C.c_double)],
         "jxs_refresh_kinematics": [vp, vp, vp, vp, C.c_int, vp],

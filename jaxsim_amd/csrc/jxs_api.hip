@@ -23,6 +23,7 @@
 #include <type_traits>
 
 #include "../../include/jaxsim_amd.h"
+#include "jxs_env_ops.h"
 #include "jxs_params.h"
 #include "jxs_pack.h"
 
@@ -457,7 +458,144 @@ __global__ void jxs_retile_kernel(const T* src, T* dst, int rows, int N, int til
   else dst[i] = src[tiled];
 }
 
+// ---- the episode loop around `step`: reset, pick and flag environments of a batch on the device (the index arithmetic
+// is jxs_env_ops.h, shared with the host harness of the tests) -------------------------------------------------------
+template <int A>
+struct alignas(A) EnvPack {
+  uint32_t u[A / 4];
+};
+
+// out[:, e] = mask[e] ? a[:, e] : b[:, e].  One wave per tile, four tiles per workgroup: the wave reads the T mask bytes
+// of its tile first (one ballot), and when none is set and the call is in place (out == b) it returns: a wave-uniform
+// exit that has cost the mask read only, no state load and no store.  Otherwise its lanes run over the contiguous
+// rows * T words of the tile in accesses of A bytes, each word of an access chosen by the mask bit of its column.
+// In place, an access none of whose words is taken is skipped too; an access all of whose words are taken loads a only.
+//
+// Access width A: the widest of 16, 8, 4 bytes that divides the byte span of ONE tile and the three block addresses
+// (jxs_env::access_bytes), because every tile starts at a multiple of that span.  The humanoid's fp32 tile is
+// 155 rows * 2 columns * 4 bytes = 1240 bytes: a multiple of 8, not of 16, so it runs with 8-byte accesses
+// (two fp32 words of one row); a 16-byte access would straddle a 16-byte line in every odd tile.  fp64 words are 8 bytes,
+// A is 8 or 16.  WB = bytes of a word.  Words move as bits (integer registers): NaN payloads, -0, denormals survive.
+template <int A, int WB>
+__global__ void __launch_bounds__(256) jxs_env_select_kernel(const uint8_t* mask, const unsigned char* a, const unsigned char* b,
+                                                             unsigned char* out, int rows, int N, int tile, long long tiles) {
+  constexpr int WPA = A / WB, UPW = WB / 4;  // words per access, 32-bit units per word
+  const int lane = threadIdx.x & 63;
+  const long long t = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (t >= tiles) return;  // (wave-uniform)
+  const bool inplace = out == b;
+  const bool narrow = tile <= 64;  // the tile's mask fits one ballot; wider tiles read the mask byte per word
+  unsigned long long bits = 0;
+  bool any;
+  if (narrow) {
+    bits = __ballot(lane < tile && jxs_env::select_takes_a(mask, jxs_env::env_of(t, lane, tile), N));
+    any = bits != 0;
+  } else {
+    bool m = false;
+    for (int c = lane; c < tile; c += 64) m = m || jxs_env::select_takes_a(mask, jxs_env::env_of(t, c, tile), N);
+    any = __ballot(m) != 0;
+  }
+  if (inplace && !any) return;
+  // (words inside a tile are counted in 32 bits -- the host refuses a tile of 2^30 words --: the column of a word is a
+  // remainder by the run-time `tile`, and a 64-bit remainder costs the lanes more than the copy itself)
+  const int per_tile = (int)jxs_env::tile_words(rows, tile);
+  const int n_acc = per_tile / WPA;  // (the host chose A so that this is exact)
+  const size_t base = (size_t)t * (size_t)per_tile * WB;
+  for (int i = lane; i < n_acc; i += 64) {
+    bool take[WPA], some = false, all = true;
+#pragma unroll
+    for (int j = 0; j < WPA; ++j) {
+      const int col = jxs_env::col_of(i * WPA + j, tile);
+      take[j] = narrow ? ((bits >> col) & 1ull) != 0 : jxs_env::select_takes_a(mask, jxs_env::env_of(t, col, tile), N);
+      some = some || take[j];
+      all = all && take[j];
+    }
+    if (inplace && !some) continue;
+    const size_t off = base + (size_t)i * A;
+    EnvPack<A> v;
+    if (all) {
+      v = *reinterpret_cast<const EnvPack<A>*>(a + off);
+    } else {
+      v = *reinterpret_cast<const EnvPack<A>*>(b + off);
+      if (some) {
+        const EnvPack<A> va = *reinterpret_cast<const EnvPack<A>*>(a + off);
+#pragma unroll
+        for (int j = 0; j < WPA; ++j)
+#pragma unroll
+          for (int u = 0; u < UPW; ++u)
+            if (take[j]) v.u[j * UPW + u] = va.u[j * UPW + u];
+      }
+    }
+    *reinterpret_cast<EnvPack<A>*>(out + off) = v;
+  }
+}
+
+// Environment src_idx[k] of `src` -> environment dst_idx[k] of `dst`, each block in its own tiling (tile 1 =
+// environment-major).  One thread per (k, row) of the flat range K * rows, rows fastest.  An entry with an index outside
+// its block is skipped whole (jxs_env::copy_pair): nothing outside the two blocks is read or written.
+template <typename W>
+__global__ void __launch_bounds__(256) jxs_env_copy_kernel(const W* src, int src_N, int src_tile, const int32_t* src_idx, W* dst, int dst_N,
+                                                           int dst_tile, const int32_t* dst_idx, int rows, long long total) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= total) return;
+  const long long k = i / rows;
+  const int row = (int)(i % rows);
+  long long se, de;
+  if (!jxs_env::copy_pair(src_idx, dst_idx, k, src_N, dst_N, &se, &de)) return;
+  dst[jxs_env::copy_dst_word(de, row, rows, dst_tile)] = src[jxs_env::copy_src_word(se, row, rows, src_tile)];
+}
+
+// One byte per environment: bit 0 = some word NaN or infinite (the rule of counts3[2] of jxs_validate_kernel), bit 1 =
+// no NaN in the quaternion and its squared norm off 1 by more than 1e-8 + 1e-5 (counts3[1]).  One wave per tile, its lanes
+// over the contiguous words of the tile: `tile` divides 64, so a lane stays in the column lane % tile over all its words,
+// and the columns are joined by a butterfly over the lanes of equal lane % tile.  Lane c < tile then evaluates the
+// quaternion rule of column c in the summation order of jxs_validate_kernel (four words the wave has just read) and is
+// the only writer of that environment's byte.  Padding columns are read and never reported.
+template <typename T>
+__global__ void __launch_bounds__(256) jxs_env_flags_kernel(const T* state, int rows, int row_quat, int tile, int N, long long tiles,
+                                                            uint8_t* out) {
+  const int lane = threadIdx.x & 63;
+  const long long t = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (t >= tiles) return;  // (wave-uniform)
+  const int per_tile = (int)jxs_env::tile_words(rows, tile);  // (the host refuses a tile of 2^30 words)
+  const T* tp = state + (size_t)t * (size_t)per_tile;
+  const long long env = jxs_env::env_of(t, lane, tile);
+  const bool writer = lane < tile && !jxs_env::is_padding(env, N);
+  // the writer's four quaternion words are asked for first, so that they travel with the words of the sweep below
+  T q[4] = {T(0), T(0), T(0), T(0)};
+  if (writer)
+    for (int k = 0; k < 4; ++k) q[k] = tp[(row_quat + k) * tile + lane];
+  int bad = 0;
+  for (int w0 = 0; w0 < per_tile; w0 += 64) {
+    const int w = w0 + lane;
+    if (w < per_tile) {
+      const T v = tp[w];
+      bad |= !(v - v == T(0));  // NaN or infinity
+    }
+  }
+  for (int o = tile; o < 64; o <<= 1) bad |= __shfl_xor(bad, o);
+  if (!writer) return;
+  T q2 = 0;
+  bool nan_q = false;
+  for (int k = 0; k < 4; ++k) {
+    const T v = q[k];
+    nan_q = nan_q || (v != v);
+    q2 += v * v;
+  }
+  const T d = q2 > T(1) ? q2 - T(1) : T(1) - q2;
+  int flags = bad ? jxs_env::kFlagNonFinite : 0;
+  if (!nan_q && !(d <= T(1e-8) + T(1e-5))) flags |= jxs_env::kFlagQuatNotUnit;
+  out[env] = (uint8_t)flags;
+}
+
 namespace {
+template <int A, int WB>
+void launch_env_select(const uint8_t* mask, const void* a, const void* b, void* out, int rows, int N, int tile, hipStream_t s) {
+  const long long tiles = jxs_env::n_tiles(N, tile);
+  hipLaunchKernelGGL((jxs_env_select_kernel<A, WB>), dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, s, mask, (const unsigned char*)a,
+                     (const unsigned char*)b, (unsigned char*)out, rows, N, tile, tiles);
+}
+
 template <typename T>
 int attach_typed(jxs_model* model, ModelT<T>* mt, int mode, const char* path) {
   const std::string want = jxs::kernel_spec_string(mt->pk, mode);
@@ -695,6 +833,72 @@ int jxs_tile_from_env_major(const void* src, void* dst, int rows, int N, int til
 }
 int jxs_tile_to_env_major(const void* src, void* dst, int rows, int N, int tile, int dtype, void* stream) {
   return retile(src, dst, rows, N, tile, dtype, stream, false);
+}
+
+int jxs_env_select(const uint8_t* mask, const void* a, const void* b, void* out, int rows, int N, int tile, int dtype, void* stream) {
+  if (mask == nullptr || a == nullptr || b == nullptr || out == nullptr) return fail(JXS_EINVAL, "null argument");
+  if (rows <= 0 || N <= 0 || tile <= 0) return fail(JXS_EINVAL, "rows, N and tile must be positive");
+  if (dtype != JXS_F32 && dtype != JXS_F64) return fail(JXS_EINVAL, "dtype must be JXS_F32 or JXS_F64");
+  const int wb = dtype == JXS_F64 ? 8 : 4;
+  const unsigned long long addr = (unsigned long long)(uintptr_t)a | (uintptr_t)b | (uintptr_t)out;
+  if (addr % wb != 0) return fail(JXS_EINVAL, "a, b and out must be aligned to their element type");
+  if (jxs_env::tile_words(rows, tile) >= (1LL << 30)) return fail(JXS_EINVAL, "rows * tile must be below 2^30");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int access = jxs_env::access_bytes(addr, rows, tile, wb);
+  if (wb == 4) {
+    if (access == 16) launch_env_select<16, 4>(mask, a, b, out, rows, N, tile, s);
+    else if (access == 8) launch_env_select<8, 4>(mask, a, b, out, rows, N, tile, s);
+    else launch_env_select<4, 4>(mask, a, b, out, rows, N, tile, s);
+  } else {
+    if (access == 16) launch_env_select<16, 8>(mask, a, b, out, rows, N, tile, s);
+    else launch_env_select<8, 8>(mask, a, b, out, rows, N, tile, s);
+  }
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(e, "jxs_env_select");
+  return JXS_OK;
+}
+
+int jxs_env_copy(const void* src, int src_N, int src_tile, const int32_t* src_idx, void* dst, int dst_N, int dst_tile,
+                 const int32_t* dst_idx, int rows, int K, int dtype, void* stream) {
+  if (src == nullptr || dst == nullptr) return fail(JXS_EINVAL, "null argument");
+  if (rows <= 0 || K <= 0 || src_N <= 0 || dst_N <= 0 || src_tile <= 0 || dst_tile <= 0)
+    return fail(JXS_EINVAL, "rows, K, src_N, dst_N, src_tile and dst_tile must be positive");
+  if (dtype != JXS_F32 && dtype != JXS_F64) return fail(JXS_EINVAL, "dtype must be JXS_F32 or JXS_F64");
+  const long long total = (long long)K * rows;
+  const int threads = 256;
+  const long long blocks = (total + threads - 1) / threads;
+  if (blocks > 0x7fffffffLL) return fail(JXS_EINVAL, "K * rows is too large for one launch");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (dtype == JXS_F64)
+    hipLaunchKernelGGL(jxs_env_copy_kernel<uint64_t>, dim3((unsigned)blocks), dim3(threads), 0, s, (const uint64_t*)src, src_N, src_tile, src_idx,
+                       (uint64_t*)dst, dst_N, dst_tile, dst_idx, rows, total);
+  else
+    hipLaunchKernelGGL(jxs_env_copy_kernel<uint32_t>, dim3((unsigned)blocks), dim3(threads), 0, s, (const uint32_t*)src, src_N, src_tile, src_idx,
+                       (uint32_t*)dst, dst_N, dst_tile, dst_idx, rows, total);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(e, "jxs_env_copy");
+  return JXS_OK;
+}
+
+int jxs_env_flags(jxs_model* model, const void* state, int N, uint8_t* out_flags, void* stream) {
+  if (model == nullptr || state == nullptr || out_flags == nullptr) return fail(JXS_EINVAL, "null argument");
+  if (N <= 0) return fail(JXS_EINVAL, "N must be positive");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int rc = with_typed(model, [&](auto* mt) {
+    using T = typename std::remove_pointer_t<decltype(mt)>::value_type;
+    const auto& P = mt->pk.P;
+    const int tile = 64 / mt->pk.G;
+    if (tile <= 0 || 64 % tile != 0) return fail(JXS_EINVAL, "jxs_env_flags: the model's tile does not divide the wave");
+    if (jxs_env::tile_words(P.n_rows, tile) >= (1LL << 30)) return fail(JXS_EINVAL, "jxs_env_flags: rows * tile must be below 2^30");
+    const long long tiles = jxs_env::n_tiles(N, tile);
+    hipLaunchKernelGGL(jxs_env_flags_kernel<T>, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, s, static_cast<const T*>(state), P.n_rows,
+                       P.row_quat, tile, N, tiles, out_flags);
+    return (int)JXS_OK;
+  });
+  if (rc != JXS_OK) return rc;
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(e, "jxs_env_flags");
+  return JXS_OK;
 }
 
 int jxs_step(jxs_model* model, const void* state_in, void* state_out, const void* tau, const void* link_forces,

@@ -377,6 +377,104 @@ class JaxSimModelData:
     def copy(self) -> "JaxSimModelData":
         return JaxSimModelData(self._model_ref, self._state.copy(), self.velocity_representation, self._batched)
 
+    # -- the episode loop around `step`: resets, gathers, scatters and flags that stay on the device ------------
+    def _check_peer(self, other, what: str, *, same_batch: bool) -> None:
+        """``other`` must hold states of the same model (the same state layout) in the same dtype -- and, for a
+        ``same_batch`` operation, as many environments in the same tiling."""
+        if not isinstance(other, JaxSimModelData):
+            raise ValueError(f"{what} must be a JaxSimModelData, not {type(other).__name__}")
+        if other._model_ref is not self._model_ref and (
+            StateLayout.of(other._model_ref) != StateLayout.of(self._model_ref) or other._state.rows != self._state.rows
+        ):
+            raise ValueError(f"{what} belongs to another model (state rows {other._state.rows} != {self._state.rows})")
+        if other.dtype != self.dtype:
+            raise ValueError(f"{what} has dtype {other.dtype}, not {self.dtype}")
+        if same_batch and (other.batch_size != self.batch_size or other._state.tile != self._state.tile):
+            raise ValueError(
+                f"{what} holds {other.batch_size} environments (tile {other._state.tile}), not {self.batch_size} (tile {self._state.tile})")
+
+    def reset_where(self, mask, fresh: "JaxSimModelData", *, inplace: bool = False) -> "JaxSimModelData":
+        """Environments whose ``mask`` entry is true take ``fresh``'s state, the others keep theirs -- the reference's
+        ``jax.tree.map(lambda a, b: jnp.where(done, a, b), fresh, data)`` under ``vmap``, as one kernel (``jxs_env_select``)
+        on the current stream: no download, no synchronisation.
+
+        ``mask``: a host bool array / sequence of ``batch_size`` entries (uploaded), a ``runtime.DeviceMask`` (for
+        instance ``env_flags()``: any non-zero byte is true), or any object with a ``__cuda_array_interface__`` of shape
+        ``(batch_size,)``, contiguous, typestr ``|b1`` or ``|u1``, which is read in place.  ``fresh`` must hold the
+        same model, dtype, batch size and tiling (``ValueError`` otherwise).  The base velocity is stored
+        inertial-fixed in both, so nothing is converted; the result keeps this object's velocity representation and
+        batched flag.  ``inplace=True`` overwrites this object's buffer and returns ``self``."""
+        self._check_peer(fresh, "fresh", same_batch=True)
+        st = self._state
+        keep, mptr = runtime.as_device_mask(mask, st.cols)
+        out = st if inplace else runtime.DeviceArray.like(st)
+        _lib.check(
+            _lib.load().jxs_env_select(mptr, fresh._state.ptr, st.ptr, out.ptr, st.rows, st.cols, st.tile, _lib.dtype_code(st.dtype), runtime._sp()),
+            "jxs_env_select",
+        )
+        del keep  # (a mask uploaded here goes back to the pool behind the launch, ordered by the stream)
+        if inplace:
+            self._invalidate_caches()
+            return self
+        return JaxSimModelData(self._model_ref, out, self.velocity_representation, self._batched)
+
+    def take(self, indices) -> "JaxSimModelData":
+        """A new data object of the ``K`` environments ``indices`` (``jax.tree.map(lambda x: x[indices], data)``), gathered
+        on the device (``jxs_env_copy``).  Host indices are checked here (``ValueError`` when out of range); indices on
+        the device (``runtime.DeviceIndices`` or a ``__cuda_array_interface__`` of typestr ``<i4``) are checked by the
+        kernel, which skips an out-of-range entry: that environment of the result is zero."""
+        st = self._state
+        keep, iptr, K, host = runtime.as_device_indices(indices, st.cols, unique=False)
+        out = runtime.DeviceArray(st.rows, K, st.dtype, tile=st.tile, zero=host is None or K % st.tile != 0)
+        _lib.check(
+            _lib.load().jxs_env_copy(
+                C.c_void_p(st.ptr), st.cols, st.tile, C.c_void_p(iptr), C.c_void_p(out.ptr), K, out.tile, None, st.rows, K,
+                _lib.dtype_code(st.dtype), runtime._sp()
+            ),
+            "jxs_env_copy",
+        )
+        del keep
+        return JaxSimModelData(self._model_ref, out, self.velocity_representation, self._batched or K != 1)
+
+    def put(self, indices, other: "JaxSimModelData", *, inplace: bool = False) -> "JaxSimModelData":
+        """Environment ``k`` of ``other`` (``K = len(indices)`` environments) replaces environment ``indices[k]``
+        (``jax.tree.map(lambda x, y: x.at[indices].set(y), data, other)``), scattered on the device.  Host indices are
+        checked here: out of range or twice the same raises ``ValueError``.  For indices on the device the kernel's
+        rule holds: an out-of-range entry is skipped, a destination named twice is left unspecified."""
+        self._check_peer(other, "other", same_batch=False)
+        st = self._state
+        keep, iptr, K, _ = runtime.as_device_indices(indices, st.cols, unique=True)
+        if other.batch_size != K:
+            raise ValueError(f"other holds {other.batch_size} environments for {K} indices")
+        out = st if inplace else st.copy()
+        _lib.check(
+            _lib.load().jxs_env_copy(
+                C.c_void_p(other._state.ptr), K, other._state.tile, None, C.c_void_p(out.ptr), st.cols, st.tile, C.c_void_p(iptr),
+                st.rows, K, _lib.dtype_code(st.dtype), runtime._sp()
+            ),
+            "jxs_env_copy",
+        )
+        del keep
+        if inplace:
+            self._invalidate_caches()
+            return self
+        return JaxSimModelData(self._model_ref, out, self.velocity_representation, self._batched)
+
+    def env_flags(self) -> runtime.DeviceMask:
+        """One byte per environment, on the device (``jxs_env_flags``): bit 0 = some state entry is NaN or infinite,
+        bit 1 = the base quaternion holds no NaN and is not of unit norm.  The result can be passed to ``reset_where``
+        as it is (every flagged environment is reset)."""
+        from .api.model import _device_model_fast  # (the look-up of `step`: no model signature per call of the hot loop)
+
+        dm = _device_model_fast(self._model_ref, self.dtype)
+        flags = runtime.DeviceMask(self.batch_size)
+        _lib.check(_lib.load().jxs_env_flags(dm.handle, self._state.ptr, self.batch_size, flags.ptr, runtime._sp()), "jxs_env_flags")
+        return flags
+
+    def nonfinite_mask(self):
+        """Bit 0 of ``env_flags()`` as a host bool array: which environments hold a NaN or an infinity."""
+        return self._out((self.env_flags().to_host() & 1) != 0)
+
 
 def random_model_data(
     model,

@@ -273,6 +273,169 @@ class DeviceArray:
         return out
 
 
+class _DeviceVector:
+    """A device vector of ``n`` small integers (environment order), pool-backed like ``DeviceArray``: its storage IS a
+    ``DeviceArray`` of one row and tile 1, so it is recycled through the same free list under the same stream rules."""
+
+    typestr = "|u1"
+
+    def __init__(self, n: int, *, zero: bool = False):
+        self.n = int(n)
+        if self.n <= 0:
+            raise ValueError("a device vector needs at least one element")
+        self._buf = DeviceArray(1, self.n, np.dtype(self.typestr), tile=1, zero=zero)
+
+    @property
+    def ptr(self):
+        return self._buf.ptr
+
+    @property
+    def shape(self):
+        return (self.n,)
+
+    @property
+    def dtype(self):
+        return self._buf.dtype
+
+    @property
+    def __cuda_array_interface__(self) -> dict:
+        return {"shape": (self.n,), "typestr": self.typestr, "data": (int(self.ptr), False), "strides": None, "version": 3}
+
+    @classmethod
+    def _upload(cls, a: np.ndarray):
+        a = np.ascontiguousarray(a, dtype=np.dtype(cls.typestr))
+        out = cls(a.shape[0])
+        _lib.check(_lib.load().jxs_memcpy_h2d(C.c_void_p(out.ptr), a.ctypes.data_as(C.c_void_p), a.nbytes, _sp()), "jxs_memcpy_h2d")
+        return out
+
+    def _download(self) -> np.ndarray:
+        out = np.empty(self.n, dtype=np.dtype(self.typestr))
+        _lib.check(_lib.load().jxs_memcpy_d2h(out.ctypes.data_as(C.c_void_p), C.c_void_p(self.ptr), out.nbytes, _sp()), "jxs_memcpy_d2h")
+        return out
+
+
+class DeviceMask(_DeviceVector):
+    """``N`` bytes on the device, one per environment, any non-zero byte true: the mask of
+    ``JaxSimModelData.reset_where`` and the result of ``env_flags``.  It exposes ``__cuda_array_interface__`` with
+    typestr ``|u1``, so another framework can fill it (or read the flags) without a copy."""
+
+    typestr = "|u1"
+
+    @staticmethod
+    def from_host(mask) -> "DeviceMask":
+        a = np.asarray(mask)
+        return DeviceMask._upload(host_mask(a, a.shape[0] if a.ndim == 1 else 1))
+
+    def to_host(self) -> np.ndarray:
+        """The bytes as they are (``uint8``): a bool mask is ``to_host() != 0``, flag bits are ``to_host() & bit``."""
+        return self._download()
+
+
+class DeviceIndices(_DeviceVector):
+    """``K`` environment indices (int32) on the device, for ``JaxSimModelData.take`` / ``put``."""
+
+    typestr = "<i4"
+
+    @staticmethod
+    def from_host(indices) -> "DeviceIndices":
+        a = np.asarray(indices)
+        if a.ndim != 1 or a.dtype.kind not in "iu" or a.shape[0] == 0:
+            raise ValueError("indices must be a non-empty 1-D integer array")
+        if a.min() < -(2**31) or a.max() >= 2**31:
+            raise ValueError("indices do not fit int32")
+        return DeviceIndices._upload(a)
+
+    def to_host(self) -> np.ndarray:
+        return self._download()
+
+
+def host_mask(mask, n: int) -> np.ndarray:
+    """A host mask (bool or integer array or sequence of ``n`` entries; a scalar for ``n == 1``) as ``n`` bytes of 0 / 1.
+    ``ValueError`` for another length or a non-boolean, non-integer dtype."""
+    a = np.asarray(mask)
+    if a.ndim == 0 and n == 1:
+        a = a.reshape(1)
+    if a.ndim != 1 or a.shape[0] != n:
+        raise ValueError(f"mask of shape {a.shape}: expected ({n},)")
+    if a.dtype.kind not in "biu":
+        raise ValueError(f"mask of dtype {a.dtype}: expected bool (or integers, non-zero = true)")
+    return (a != 0).astype(np.uint8)
+
+
+def host_indices(indices, bound: int, *, unique: bool) -> np.ndarray:
+    """Host indices (1-D integers; a scalar counts as one) as int32, each in ``[0, bound)`` and, if ``unique``, no index
+    twice: ``ValueError`` otherwise.  (Indices that live on the device cannot be checked here: the kernel skips the bad
+    ones, see ``jxs_env_copy``.)"""
+    a = np.asarray(indices)
+    if a.ndim == 0:
+        a = a.reshape(1)
+    if a.ndim != 1 or a.shape[0] == 0:
+        raise ValueError(f"indices of shape {a.shape}: expected a non-empty 1-D array")
+    if a.dtype.kind not in "iu":
+        raise ValueError(f"indices of dtype {a.dtype}: expected integers")
+    if a.min() < 0 or a.max() >= bound:
+        raise ValueError(f"indices out of range [0, {bound})")
+    if unique and np.unique(a).shape[0] != a.shape[0]:
+        raise ValueError("duplicate indices")
+    return a.astype(np.int32)
+
+
+def foreign_vector(obj, n: int | None, typestrs: tuple) -> tuple[int, int]:
+    """``(device pointer, length)`` of an object that speaks ``__cuda_array_interface__``, used with ZERO copy: it must
+    be 1-D (of ``n`` entries, if given), contiguous, and of one of ``typestrs``; ``ValueError`` otherwise.  The caller
+    keeps ``obj`` alive and is responsible for the ordering between the stream that wrote it and the current one."""
+    cai = obj.__cuda_array_interface__
+    shape = tuple(cai["shape"])
+    if len(shape) != 1 or shape[0] <= 0 or (n is not None and shape[0] != n):
+        raise ValueError(f"device array of shape {shape}: expected ({'K' if n is None else n},)")
+    if cai["typestr"] not in typestrs:
+        raise ValueError(f"device array of typestr {cai['typestr']!r}: expected one of {typestrs}")
+    itemsize = np.dtype(cai["typestr"]).itemsize
+    strides = cai.get("strides")
+    if strides is not None and tuple(strides) != (itemsize,) and shape[0] > 1:
+        raise ValueError("device array must be contiguous")
+    ptr = cai["data"][0]
+    if not ptr:
+        raise ValueError("device array with a null pointer")
+    return int(ptr), int(shape[0])
+
+
+MASK_TYPESTRS = ("|b1", "|u1")
+INDEX_TYPESTRS = ("<i4",)
+
+
+def as_device_mask(mask, n: int):
+    """``(object to keep alive until the launch is enqueued, device pointer)`` of a mask argument: a ``DeviceMask``, any
+    object with a ``__cuda_array_interface__`` of shape ``(n,)`` and typestr ``|b1`` / ``|u1`` (zero copy), or a host
+    array / sequence (uploaded).  Anything else: ``ValueError``."""
+    if isinstance(mask, DeviceMask):
+        if mask.n != n:
+            raise ValueError(f"mask of {mask.n} entries: expected {n}")
+        return mask, mask.ptr
+    if isinstance(mask, _DeviceVector):
+        raise ValueError(f"mask of typestr {mask.typestr!r}: expected one of {MASK_TYPESTRS}")
+    if hasattr(mask, "__cuda_array_interface__"):
+        return mask, foreign_vector(mask, n, MASK_TYPESTRS)[0]
+    dm = DeviceMask._upload(host_mask(mask, n))
+    return dm, dm.ptr
+
+
+def as_device_indices(indices, bound: int, *, unique: bool):
+    """``(keep-alive, device pointer, K, host copy or None)`` of an index argument: ``DeviceIndices`` or a
+    ``__cuda_array_interface__`` of typestr ``<i4`` (zero copy, checked by the kernel only), or host integers (checked
+    here against ``[0, bound)`` and, if ``unique``, for duplicates; then uploaded)."""
+    if isinstance(indices, DeviceIndices):
+        return indices, indices.ptr, indices.n, None
+    if isinstance(indices, _DeviceVector):
+        raise ValueError(f"indices of typestr {indices.typestr!r}: expected one of {INDEX_TYPESTRS}")
+    if hasattr(indices, "__cuda_array_interface__"):
+        ptr, k = foreign_vector(indices, None, INDEX_TYPESTRS)
+        return indices, ptr, k, None
+    h = host_indices(indices, bound, unique=unique)
+    di = DeviceIndices._upload(h)
+    return di, di.ptr, di.n, h
+
+
 def trim_pool() -> None:
     """Return every pooled buffer to the driver."""
     lib = _lib.load()
