@@ -309,6 +309,23 @@ int jxs_env_copy(const void* src, int src_N, int src_tile, const int32_t* src_id
 enum { JXS_ENV_NONFINITE = 1, JXS_ENV_QUAT_NOT_UNIT = 2 };
 int jxs_env_flags(jxs_model* model, const void* state, int N, uint8_t* out_flags, void* stream);
 
+/* jxs_env_randomize: a freshly sampled state into exactly the environments `mask` names (N bytes on the device, any
+ *   non-zero byte is true, never read at or beyond N; NULL = every environment), in place on the tile-interleaved block
+ *   of `model`'s layout and dtype -- the reference's `jnp.where(done, random_model_data(model, key=k), data)` under vmap
+ *   without a `fresh` block.  The other environments and the padding columns of the last tile keep every bit.
+ *   `bounds` = [2][12 + 2 n_joints] words of the state's dtype on the device, the row of lower and the row of upper
+ *   bounds of the variables: 0-2 base position, 3-5 XYZ Euler angles, 6.. joint positions, then 3 linear and 3 angular
+ *   base-velocity components in `velocity_representation` (JXS_REPR_*; stored inertial-fixed; zeros for a fixed base),
+ *   then the joint velocities.  The rows behind the joint velocities (tangential deformation) are written as zero.
+ *   A value is a function of (seed, draw, first_env + e, variable) alone -- Philox4x32-10 with key = seed and counter =
+ *   (first_env + e, variable, draw), csrc/jxs_env_random.h --, never of N, the tiling, the mask or the split of a batch
+ *   over processes: a shard passes the global index of its first environment as `first_env` and draws what one big
+ *   batch would.  Asynchronous on `stream`; no allocation, synchronisation or host read (legal between two jxs_step
+ *   launches and inside a stream capture: a captured graph replays the same `draw`).  JXS_EINVAL: a null model, state
+ *   or bounds, N <= 0, first_env < 0, first_env + N > 2^32, an unknown representation, a misaligned block.          */
+int jxs_env_randomize(jxs_model* model, const uint8_t* mask, void* state, int N, const void* bounds, uint64_t seed,
+                      uint64_t draw, int64_t first_env, int velocity_representation, void* stream);
+
 /* RigidContacts only.  A contact-force QP or an impact solve whose result is not finite (fp32 on a numerically
  * singular stance) is DISCARDED -- that environment takes the step without contact forces / without the
  * velocity reset instead of poisoning its state -- where the reference would propagate NaN

@@ -1,3 +1,9 @@
 """``jaxsim.api.data`` mirror (``src/jaxsim/api/data.py``)."""
 
-from ..data import JaxSimModelData, random_model_data  # noqa: F401
+from ..data import (  # noqa: F401
+    JaxSimModelData,
+    RandomStateDistribution,
+    random_model_data,
+    random_model_data_device,
+    random_state_bounds,
+)

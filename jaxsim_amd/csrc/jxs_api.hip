@@ -24,6 +24,7 @@
 
 #include "../../include/jaxsim_amd.h"
 #include "jxs_env_ops.h"
+#include "jxs_env_random.h"
 #include "jxs_params.h"
 #include "jxs_pack.h"
 
@@ -588,6 +589,83 @@ __global__ void __launch_bounds__(256) jxs_env_flags_kernel(const T* state, int 
   out[env] = (uint8_t)flags;
 }
 
+// A freshly sampled state into the environments the mask names, in place (the sampler is jxs_env_random.h: every word
+// is jxs_rand::row_value of its row and its global environment).  One wave per tile, four tiles per workgroup, like
+// jxs_env_select: the wave reads the T mask bytes of its tile first (one ballot; a null mask names every environment)
+// and returns when none is set -- the sparse reset of a large batch costs the mask read only.  Otherwise, in its own
+// slice of LDS ((12 + 2n + 10) * T words):
+//   1. its lanes draw the 12 + 2n variables of the T environments, one Philox block each (jxs_rand::variable);
+//   2. 10 T lanes compute the rows that are no variable -- quaternion, converted base velocity -- from them
+//      (jxs_rand::derived_value: the sines and cosines run once per environment, not once per word);
+//   3. its lanes run over the contiguous rows * T words of the tile in accesses of A bytes (the widest the tile span and
+//      the block address allow, jxs_env::access_bytes), each word placed by jxs_rand::row_source: an access none of whose
+//      columns is named is skipped, one all of whose columns are named is stored without a load, a mixed one is loaded,
+//      patched and stored.  Padding columns are never named.
+// The three steps of one wave follow each other in program order and LDS serves a wave's accesses in order; the fences
+// keep the compiler from moving them.  No workgroup barrier: the waves of a workgroup share nothing and may have left.
+// `tile` divides 64 (the host checks), so the column and the row of a word are a mask and a shift.
+template <typename T, int A>
+__global__ void __launch_bounds__(256) jxs_env_randomize_kernel(const uint8_t* mask, unsigned char* state, int rows, int N, int tile_shift,
+                                                                long long tiles, jxs_rand::Shape shape, const T* bounds, uint64_t seed,
+                                                                uint64_t draw, long long first_env) {
+  constexpr int WB = sizeof(T), WPA = A / WB;  // bytes per word, words per access
+  extern __shared__ __align__(16) unsigned char jxs_randomize_lds[];
+  const int tile = 1 << tile_shift;
+  const int lane = threadIdx.x & 63;
+  const long long t = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (t >= tiles) return;  // (wave-uniform)
+  const long long env = jxs_env::env_of(t, lane, tile);
+  const unsigned long long bits = __ballot(lane < tile && !jxs_env::is_padding(env, N) && (mask == nullptr || mask[env] != 0));
+  if (bits == 0) return;  // (wave-uniform)
+  const int nv = jxs_rand::n_variables(shape.n_joints);
+  T* vars = reinterpret_cast<T*>(jxs_randomize_lds) + (size_t)(threadIdx.x >> 6) * (size_t)((nv + jxs_rand::kDerived) << tile_shift);
+  T* derived = vars + ((size_t)nv << tile_shift);  // [kDerived][T] behind [nv][T]
+  const uint32_t env0 = (uint32_t)(first_env + t * tile);  // (the host checked that every named environment fits 32 bits)
+  for (int i = lane; i < (nv << tile_shift); i += 64) {
+    const int col = i & (tile - 1);
+    if ((bits >> col) & 1ull) vars[i] = jxs_rand::variable(bounds, nv, i >> tile_shift, seed, draw, env0 + (uint32_t)col);
+  }
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  for (int i = lane; i < (jxs_rand::kDerived << tile_shift); i += 64) {
+    const int col = i & (tile - 1), d = i >> tile_shift;
+    // (a value no row takes -- the velocity of a fixed base, of the Inertial representation -- is not computed)
+    const bool used = d < 4 || (shape.floating && (shape.repr == jxs_rand::kReprBody || (shape.repr == jxs_rand::kReprMixed && d < 7)));
+    if (used && ((bits >> col) & 1ull)) derived[i] = jxs_rand::derived_value<T>(shape, d, [&](int v) { return vars[(v << tile_shift) + col]; });
+  }
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  const int per_tile = (int)jxs_env::tile_words(rows, tile);  // (the host refuses a tile of 2^30 words)
+  const int n_acc = per_tile / WPA;                            // (the host chose A so that this is exact)
+  unsigned char* tp = state + (size_t)t * (size_t)per_tile * WB;
+  for (int i = lane; i < n_acc; i += 64) {
+    bool take[WPA], some = false, all = true;
+#pragma unroll
+    for (int j = 0; j < WPA; ++j) {
+      take[j] = ((bits >> ((i * WPA + j) & (tile - 1))) & 1ull) != 0;
+      some = some || take[j];
+      all = all && take[j];
+    }
+    if (!some) continue;
+    EnvPack<A>* p = reinterpret_cast<EnvPack<A>*>(tp + (size_t)i * A);
+    EnvPack<A> v;
+    if (!all) v = *p;
+#pragma unroll
+    for (int j = 0; j < WPA; ++j) {
+      if (!take[j]) continue;
+      const int w = i * WPA + j, col = w & (tile - 1);
+      const jxs_rand::RowSource src = jxs_rand::row_source(shape, w >> tile_shift);
+      T x = T(0);
+      if (src.kind == jxs_rand::kRowVariable) x = vars[(src.index << tile_shift) + col];
+      else if (src.kind == jxs_rand::kRowDerived) x = derived[(src.index << tile_shift) + col];
+      __builtin_memcpy(&v.u[j * (WB / 4)], &x, WB);
+    }
+    *p = v;
+  }
+}
+
 namespace {
 template <int A, int WB>
 void launch_env_select(const uint8_t* mask, const void* a, const void* b, void* out, int rows, int N, int tile, hipStream_t s) {
@@ -898,6 +976,52 @@ int jxs_env_flags(jxs_model* model, const void* state, int N, uint8_t* out_flags
   if (rc != JXS_OK) return rc;
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return hip_fail(e, "jxs_env_flags");
+  return JXS_OK;
+}
+
+int jxs_env_randomize(jxs_model* model, const uint8_t* mask, void* state, int N, const void* bounds, uint64_t seed, uint64_t draw,
+                      int64_t first_env, int velocity_representation, void* stream) {
+  if (model == nullptr || state == nullptr || bounds == nullptr) return fail(JXS_EINVAL, "null argument");
+  if (N <= 0) return fail(JXS_EINVAL, "N must be positive");
+  if (!jxs_rand::env_range_ok(first_env, N)) return fail(JXS_EINVAL, "jxs_env_randomize: first_env must be >= 0 and first_env + N <= 2^32");
+  if (velocity_representation != JXS_REPR_INERTIAL && velocity_representation != JXS_REPR_BODY && velocity_representation != JXS_REPR_MIXED)
+    return fail(JXS_EINVAL, "jxs_env_randomize: unknown velocity representation");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int rc = with_typed(model, [&](auto* mt) {
+    using T = typename std::remove_pointer_t<decltype(mt)>::value_type;
+    const auto& P = mt->pk.P;
+    const int tile = 64 / mt->pk.G;
+    int tile_shift = 0;
+    while ((1 << tile_shift) < tile) ++tile_shift;
+    if (tile <= 0 || (1 << tile_shift) != tile || tile > 64) return fail(JXS_EINVAL, "jxs_env_randomize: the model's tile does not divide the wave");
+    if (jxs_env::tile_words(P.n_rows, tile) >= (1LL << 30)) return fail(JXS_EINVAL, "jxs_env_randomize: rows * tile must be below 2^30");
+    if ((uintptr_t)state % sizeof(T) != 0 || (uintptr_t)bounds % sizeof(T) != 0)
+      return fail(JXS_EINVAL, "jxs_env_randomize: state and bounds must be aligned to their element type");
+    const jxs_rand::Shape shape{P.n, P.floating, velocity_representation};
+    // LDS of a workgroup: four waves, each the variables and the derived values of the T environments of its tile.
+    // The packer gives an environment G >= max(4, pow2ceil(n_links)) lanes (jxs_pack.h), so T = 64 / G <= 16 and
+    // n_joints < G: a wave needs at most (22 + 2 G) * 64 / G <= 480 words, a workgroup at most 15 KB in fp64.  The
+    // refusal below cannot be reached with that rule; it is there so that a packer that ever allowed more (T = 64 with
+    // many joints) fails here with a message instead of launching with more LDS than a workgroup may have -- the
+    // remedy then is fewer waves per workgroup, not a larger limit.
+    const size_t lds = 4 * (size_t)(jxs_rand::n_variables(P.n) + jxs_rand::kDerived) * tile * sizeof(T);
+    if (lds > 65536) return fail(JXS_EINVAL, "jxs_env_randomize: (12 + 2 n_joints + 10) * tile words per wave do not fit the LDS of a workgroup");
+    const long long tiles = jxs_env::n_tiles(N, tile);
+    const dim3 grid((unsigned)((tiles + 3) / 4)), block(256);
+    unsigned char* st = static_cast<unsigned char*>(state);
+    const T* bd = static_cast<const T*>(bounds);
+    const int access = jxs_env::access_bytes((unsigned long long)(uintptr_t)state, P.n_rows, tile, (int)sizeof(T));
+#define JXS_RANDOMIZE(A) \
+  hipLaunchKernelGGL((jxs_env_randomize_kernel<T, A>), grid, block, lds, s, mask, st, P.n_rows, N, tile_shift, tiles, shape, bd, seed, draw, (long long)first_env)
+    if (access == 16) JXS_RANDOMIZE(16);
+    else if (access == 8) JXS_RANDOMIZE(8);
+    else if constexpr (sizeof(T) == 4) JXS_RANDOMIZE(4);
+#undef JXS_RANDOMIZE
+    return (int)JXS_OK;
+  });
+  if (rc != JXS_OK) return rc;
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(e, "jxs_env_randomize");
   return JXS_OK;
 }
 

@@ -418,6 +418,48 @@ class JaxSimModelData:
             return self
         return JaxSimModelData(self._model_ref, out, self.velocity_representation, self._batched)
 
+    def reset_random_where(self, mask, dist: "RandomStateDistribution", *, seed: int = 0, draw: int = 0, first_env: int = 0,
+                           inplace: bool = False) -> "JaxSimModelData":
+        """Environments whose ``mask`` entry is true take a freshly sampled state of ``dist``, the others keep theirs -- the
+        reference's ``jnp.where(done, random_model_data(model, key=k), data)`` under ``vmap`` as one kernel
+        (``jxs_env_randomize``) on the current stream, with no ``fresh`` block: no allocation, download or synchronisation.
+
+        ``mask``: as for ``reset_where`` (host bools, a ``runtime.DeviceMask`` such as ``env_flags()``, or a
+        ``__cuda_array_interface__`` of bytes); ``None`` means every environment.  The state of environment ``e`` is a
+        function of ``(seed, draw, first_env + e)`` and the bounds alone -- not of the batch size, the mask or the tiling --
+        so an episode loop passes a new ``draw`` per reset, and a shard of a larger batch passes the global index of its
+        first environment as ``first_env`` and draws what the whole batch would.  ``dist`` must have been built for this
+        model layout and dtype (``ValueError`` otherwise); the sampled base velocity is expressed in ``dist``'s velocity
+        representation and stored inertial-fixed.  ``inplace=True`` overwrites this object's buffer and returns ``self``;
+        otherwise the block is copied first."""
+        from .api.model import _device_model_fast
+
+        if not isinstance(dist, RandomStateDistribution):
+            raise ValueError(f"dist must be a RandomStateDistribution, not {type(dist).__name__}")
+        st = self._state
+        if dist.layout != StateLayout.of(self._model_ref) or dist.layout.n_rows != st.rows:
+            raise ValueError(f"dist was built for another model layout ({dist.layout} != {StateLayout.of(self._model_ref)})")
+        if dist.dtype != self.dtype:
+            raise ValueError(f"dist was built for dtype {dist.dtype}, not {self.dtype}")
+        seed, draw, first_env = int(seed), int(draw), int(first_env)
+        if not (0 <= seed < 2**64 and 0 <= draw < 2**64):
+            raise ValueError("seed and draw must fit 64 unsigned bits")
+        if first_env < 0 or first_env + st.cols > 2**32:
+            raise ValueError(f"first_env = {first_env} with {st.cols} environments: global environment indices must stay below 2^32")
+        keep, mptr = (None, None) if mask is None else runtime.as_device_mask(mask, st.cols)
+        dm = _device_model_fast(self._model_ref, self.dtype)
+        out = st if inplace else st.copy()
+        _lib.check(
+            _lib.load().jxs_env_randomize(dm.handle, mptr, out.ptr, st.cols, dist.bounds_ptr, seed, draw, first_env,
+                                          int(dist.velocity_representation), runtime._sp()),
+            "jxs_env_randomize",
+        )  # fmt: skip
+        del keep
+        if inplace:
+            self._invalidate_caches()
+            return self
+        return JaxSimModelData(self._model_ref, out, self.velocity_representation, self._batched)
+
     def take(self, indices) -> "JaxSimModelData":
         """A new data object of the ``K`` environments ``indices`` (``jax.tree.map(lambda x: x[indices], data)``), gathered
         on the device (``jxs_env_copy``).  Host indices are checked here (``ValueError`` when out of range); indices on
@@ -517,3 +559,124 @@ def random_model_data(
         batch_size=N,
         dtype=dtype,
     )
+
+
+def _bounds_pair(bounds, width: int, what: str) -> np.ndarray:
+    """``(lo, hi)``, each a scalar or a sequence of ``width`` entries, as a ``[2, width]`` float64 array."""
+    if len(bounds) != 2:
+        raise ValueError(f"{what} must be a pair (lower, upper)")
+    out = np.empty((2, width))
+    for k in range(2):
+        a = np.asarray(bounds[k], dtype=float)
+        if a.ndim > 1 or (a.ndim == 1 and a.shape[0] not in (1, width)):
+            raise ValueError(f"{what}[{k}] of shape {a.shape}: expected a scalar or {width} entries")
+        out[k] = a
+    return out
+
+
+def random_state_bounds(
+    model,
+    *,
+    dtype=np.float32,
+    base_pos_bounds=((-1, -1, 0.5), 1.0),
+    base_rpy_bounds=(-np.pi, np.pi),
+    joint_pos_bounds=None,
+    base_vel_lin_bounds=(-1.0, 1.0),
+    base_vel_ang_bounds=(-1.0, 1.0),
+    joint_vel_bounds=(-1.0, 1.0),
+) -> np.ndarray:
+    """The host bounds table ``[2][12 + 2n]`` of ``jxs_env_randomize`` (row of lower, row of upper bounds, rounded to
+    ``dtype``) from the arguments of the reference's ``random_model_data`` (``src/jaxsim/api/data.py:552-586``: the same
+    defaults, each bound a scalar or one value per component).  Variables: 3 base position, 3 XYZ Euler angles, n joint
+    positions, 3 linear and 3 angular base velocity, n joint velocities.  ``joint_pos_bounds=None``: the joint limits by
+    the rule of ``js.joint.random_joint_positions``.  ``ValueError`` for a bound that is not finite in ``dtype`` or
+    lies above its partner."""
+    from .api import joint as _joint
+
+    n = model.kin_dyn_parameters.number_of_joints()
+    dt = np.dtype(dtype)
+    _lib.dtype_code(dt)
+    if joint_pos_bounds is None:
+        s = np.stack(_joint.random_position_bounds(model, dtype=dt)).astype(float) if n else np.empty((2, 0))
+    else:
+        s = _bounds_pair(joint_pos_bounds, n, "joint_pos_bounds")
+    table = np.concatenate(
+        [
+            _bounds_pair(base_pos_bounds, 3, "base_pos_bounds"),
+            _bounds_pair(base_rpy_bounds, 3, "base_rpy_bounds"),
+            s,
+            _bounds_pair(base_vel_lin_bounds, 3, "base_vel_lin_bounds"),
+            _bounds_pair(base_vel_ang_bounds, 3, "base_vel_ang_bounds"),
+            _bounds_pair(joint_vel_bounds, n, "joint_vel_bounds"),
+        ],
+        axis=1,
+    )
+    with np.errstate(over="ignore", invalid="ignore"):
+        table = table.astype(dt)
+        finite = np.isfinite(table).all(axis=0) & np.isfinite(table[1] - table[0])
+    if not finite.all():
+        raise ValueError(f"bounds of the variables {np.nonzero(~finite)[0].tolist()} are not finite in {dt.name}: "
+                         "pass explicit finite bounds (joint_pos_bounds for joints without position limits)")
+    if (table[0] > table[1]).any():
+        raise ValueError(f"lower bound above upper bound for the variables {np.nonzero(table[0] > table[1])[0].tolist()}")
+    return np.ascontiguousarray(table)
+
+
+class RandomStateDistribution:
+    """The uniform distribution of reset states of one model, with its bounds table resident on the device: what
+    ``JaxSimModelData.reset_random_where`` and ``random_model_data_device`` sample from.  Built once (one small upload),
+    used for every reset of an episode loop."""
+
+    def __init__(self, layout: StateLayout, dtype, velocity_representation: VelRepr, bounds_host: np.ndarray):
+        self.layout = layout
+        self.dtype = np.dtype(dtype)
+        self.velocity_representation = VelRepr(velocity_representation)
+        self.bounds_host = bounds_host  # [2, 12 + 2n], in `dtype`
+        self._bounds = runtime.DeviceArray(1, bounds_host.size, self.dtype, tile=1)  # (flat: one row, environment-major)
+        _lib.check(
+            _lib.load().jxs_memcpy_h2d(C.c_void_p(self._bounds.ptr), bounds_host.ctypes.data_as(C.c_void_p), bounds_host.nbytes, runtime._sp()),
+            "jxs_memcpy_h2d",
+        )
+        # the one-off upload is waited for here: the table may be read by a reset on ANY stream afterwards
+        # (runtime.set_stream between build and use), and nothing else would order that stream behind this copy
+        runtime.synchronize()
+
+    @property
+    def bounds_ptr(self):
+        return self._bounds.ptr
+
+    @staticmethod
+    def build(model, *, dtype=np.float32, velocity_representation: VelRepr = VelRepr.Mixed, **bounds) -> "RandomStateDistribution":
+        """``bounds``: ``base_pos_bounds``, ``base_rpy_bounds``, ``joint_pos_bounds``, ``base_vel_lin_bounds``,
+        ``base_vel_ang_bounds``, ``joint_vel_bounds`` as for ``random_state_bounds`` (the reference's defaults)."""
+        runtime.require_device()
+        table = random_state_bounds(model, dtype=dtype, **bounds)
+        return RandomStateDistribution(StateLayout.of(model), dtype, velocity_representation, table)
+
+
+def random_model_data_device(
+    model,
+    *,
+    batch_size: int,
+    dist: RandomStateDistribution | None = None,
+    seed: int = 0,
+    draw: int = 0,
+    first_env: int = 0,
+    dtype=np.float32,
+    **bounds,
+) -> JaxSimModelData:
+    """A new batch of ``batch_size`` random states filled entirely on the device (``jxs_env_randomize`` over every
+    environment): no host sampling, packing or upload.  ``dist``: a ``RandomStateDistribution`` to reuse; otherwise one is
+    built from ``dtype`` and ``bounds`` (``velocity_representation`` and the bounds of ``random_state_bounds``).  The state
+    of environment ``e`` is the one ``reset_random_where`` gives it for the same ``(seed, draw, first_env)``.  The host
+    ``random_model_data`` (NumPy's PCG64) is a different stream."""
+    if dist is None:
+        dist = RandomStateDistribution.build(model, dtype=dtype, **bounds)
+    elif bounds:
+        raise ValueError(f"pass either dist or bounds, not both ({sorted(bounds)})")
+    if int(batch_size) <= 0:
+        raise ValueError("batch_size must be positive")
+    tile = runtime.device_model(model, dist.dtype).layout.tile
+    state = runtime.DeviceArray(dist.layout.n_rows, int(batch_size), dist.dtype, tile=tile, zero=int(batch_size) % tile != 0)
+    data = JaxSimModelData(model, state, dist.velocity_representation, True)
+    return data.reset_random_where(None, dist, seed=seed, draw=draw, first_env=first_env, inplace=True)

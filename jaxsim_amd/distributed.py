@@ -8,6 +8,11 @@ only for bootstrap -- broadcasting the 128-byte RCCL unique id, barriers, and th
 reduction of ``bench.py`` -- while the data path goes through ``jxs_allgather`` (RCCL called
 from the C-ABI library on raw device pointers).  On a machine without GPUs (the CPU tests,
 ``gloo`` backend) the same host logic gathers through ``torch.distributed`` instead.
+
+Random resets need no communication either: the state ``JaxSimModelData.reset_random_where`` /
+``random_model_data_device`` draw for an environment depends on ``(seed, draw)`` and the GLOBAL
+index of the environment only.  The rule: a rank passes ``first_env = shard_bounds(...)[0]``, the
+global index of its shard's first environment, and the shards draw what one big batch would.
 """
 
 from __future__ import annotations
