@@ -326,6 +326,48 @@ int jxs_env_flags(jxs_model* model, const void* state, int N, uint8_t* out_flags
 int jxs_env_randomize(jxs_model* model, const uint8_t* mask, void* state, int N, const void* bounds, uint64_t seed,
                       uint64_t draw, int64_t first_env, int velocity_representation, void* stream);
 
+/* jxs_env_observe: the input of a policy network, an environment-major tensor `out` = [N][out_ld], assembled on the
+ *   device from the tiled state block and up to four further tiled blocks [rows_s][N] of the state's dtype and tile (the
+ *   centroidal record, frame records, gravity torques, link contact wrenches, last step's torques ...) -- what the
+ *   reference's user gets from `jnp.concatenate` of `data.joint_positions`, `data.base_orientation`, `data.base_velocity`
+ *   ... under vmap (src/jaxsim/api/data.py:267-312, inertial_to_other_representation of api/common.py:100-158).
+ *   The observation is described once per model by an immutable table of D slots (1 <= D <= JXS_OBS_MAX_WIDTH), slot d =
+ *   {kind, source, index} with `offset[d]` and `scale[d]` (NULL: zeros / ones; rounded to the model's dtype): word d of
+ *   environment e is (x - offset[d]) * scale[d], two roundings in the state's dtype, with x by kind:
+ *     JXS_OBS_STATE_ROW          word `index` of the environment's state rows (jxs_layout order)
+ *     JXS_OBS_SOURCE_ROW         row `index` of block `source` (0 .. 3), which has `source_rows[source]` rows
+ *     JXS_OBS_BASE_QUAT_UNIT     component `index` (w x y z) of q / |q|; a zero quaternion stays as it is
+ *     JXS_OBS_BASE_ROTATION      entry `index` (0 .. 8, row-major) of the rotation matrix of q / |q|
+ *     JXS_OBS_BASE_VELOCITY      component `index` (0-2 linear, 3-5 angular) of the base velocity in the launch's
+ *                                `velocity_representation` (JXS_REPR_*; the state stores it inertial-fixed)
+ *     JXS_OBS_PROJECTED_GRAVITY  component `index` of R^T (0, 0, -1)
+ *   jxs_observation_create refuses with JXS_EINVAL: D outside its range, an unknown kind, a row, component or source out
+ *   of range (a source whose `source_rows` entry is <= 0 does not exist; NULL `source_rows`: none does), an offset or
+ *   scale that is not finite in the model's dtype.  A table may be used with every model of the same state layout and dtype.
+ *   jxs_env_observe writes columns < D of rows < N of `out` and nothing else: with out_ld > D a caller fills a slice of a
+ *   wider tensor.  `out_dtype` is JXS_F32 or the model's dtype (an fp64 state is rounded once, at the store).  The four
+ *   source pointers travel by value; one the table does not use may be NULL.  Padding columns of the last tile are
+ *   never read as environments and no source is read beyond its storage.  Asynchronous on `stream`; no allocation,
+ *   synchronisation, memset or host read (legal between two jxs_step launches and inside a stream capture).  JXS_EINVAL:
+ *   a null model, table, state or out, N <= 0, out_ld < D, an unknown representation or out_dtype, a used source whose
+ *   pointer is NULL, a table of another layout or dtype, a misaligned block.                                            */
+#define JXS_OBS_MAX_WIDTH 4096
+enum {
+  JXS_OBS_STATE_ROW = 0,
+  JXS_OBS_SOURCE_ROW = 1,
+  JXS_OBS_BASE_QUAT_UNIT = 2,
+  JXS_OBS_BASE_ROTATION = 3,
+  JXS_OBS_BASE_VELOCITY = 4,
+  JXS_OBS_PROJECTED_GRAVITY = 5
+};
+typedef struct jxs_observation jxs_observation;
+int jxs_observation_create(jxs_model* model, int D, const int32_t* slots /* [D][3] */, const double* offset,
+                           const double* scale, const int32_t source_rows[4], jxs_observation** out);
+int jxs_observation_destroy(jxs_observation* observation);
+int jxs_env_observe(jxs_model* model, const jxs_observation* observation, const void* state,
+                    const void* const sources[4], int N, int velocity_representation, void* out, int out_dtype,
+                    int64_t out_ld, void* stream);
+
 /* RigidContacts only.  A contact-force QP or an impact solve whose result is not finite (fp32 on a numerically
  * singular stance) is DISCARDED -- that environment takes the step without contact forces / without the
  * velocity reset instead of poisoning its state -- where the reference would propagate NaN

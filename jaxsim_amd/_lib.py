@@ -243,6 +243,9 @@ def _declare(lib):
         "jxs_env_copy": [vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp],
         "jxs_env_flags": [vp, vp, C.c_int, vp, vp],
         "jxs_env_randomize": [vp, vp, vp, C.c_int, vp, C.c_uint64, C.c_uint64, C.c_int64, C.c_int, vp],
+        "jxs_observation_create": [vp, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(vp)],
+        "jxs_observation_destroy": [vp],
+        "jxs_env_observe": [vp, vp, vp, C.POINTER(vp), C.c_int, C.c_int, vp, C.c_int, C.c_int64, vp],
         "jxs_step_repeat": [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp],
         "jxs_step_repeat_timed": [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, C.POINTER(C.c_double)],
         "jxs_refresh_kinematics": [vp, vp, vp, vp, C.c_int, vp],

@@ -2,6 +2,7 @@
 
 from ..data import (  # noqa: F401
     JaxSimModelData,
+    ObservationSpec,
     RandomStateDistribution,
     random_model_data,
     random_model_data_device,

@@ -23,6 +23,7 @@
 #include <type_traits>
 
 #include "../../include/jaxsim_amd.h"
+#include "jxs_env_observe.h"
 #include "jxs_env_ops.h"
 #include "jxs_env_random.h"
 #include "jxs_params.h"
@@ -50,7 +51,10 @@ namespace {
 // with a Python thread that changes os.environ (glibc getenv against setenv).  jxs_debug_reload_env() re-reads them: the
 // tests switch variants between launches of one process.  Launches captured in a hipGraph keep what they captured.
 std::atomic<int> g_knobs{-1}, g_duo_max_blocks{0};
+std::atomic<int> g_observe_envs_per_wave{0};  // JXS_OBSERVE_ENVS_PER_WAVE: 0 = the launcher's own rule (tools/bench_env_observe.py)
 void load_knobs() {
+  const char* ow = std::getenv("JXS_OBSERVE_ENVS_PER_WAVE");
+  g_observe_envs_per_wave.store(ow == nullptr ? 0 : std::atoi(ow));
   auto on = [](const char* name) { const char* v = std::getenv(name); return v != nullptr && std::atoi(v) != 0; };
   int k = 0;
   if (on("JXS_NO_MFMA")) k |= jxs::KNOB_NO_MFMA;
@@ -159,6 +163,18 @@ struct jxs_frames {
   const jxs_model* owner = nullptr;
   int n = 0;
   void* tgt = nullptr;  // [n][jxs::kTgtStride] in the precision of the owner
+};
+
+// an immutable observation table on the device (jxs_observation_create): per slot its packed word (jxs_obs::pack_slot),
+// offset and scale, in one allocation [codes | offset | scale]
+struct jxs_observation {
+  int dtype = JXS_F32;
+  int D = 0, n_rows = 0, n_joints = 0;
+  int32_t source_rows[jxs_obs::kSources] = {0, 0, 0, 0};
+  unsigned sources_used = 0;         // bit s: some slot reads source s
+  unsigned derived_used[3] = {0, 0, 0};  // per JXS_REPR_*: the derived values a launch computes (jxs_obs::derived_used)
+  void* table = nullptr;             // device
+  size_t offset_at = 0, scale_at = 0;  // bytes from `table`
 };
 
 struct jxs_model {
@@ -666,6 +682,88 @@ __global__ void __launch_bounds__(256) jxs_env_randomize_kernel(const uint8_t* m
   }
 }
 
+// The observation tensor out[N][out_ld] of a policy (the slots are jxs_env_observe.h: every word is jxs_obs::slot_value of
+// its slot and its environment).  A wave takes E = 2^env_shift consecutive environments -- whole tiles, E >= T --, four
+// waves per workgroup that share nothing:
+//   1. its lanes compute the unit quaternion of the E environments, 4 E values (jxs_obs::unit_quaternion_component), and
+//   2. from those the other derived values a slot of the table reads, up to 18 E (jxs_obs::derived_from_unit), into the
+//      wave's slice of LDS, [kDerived][E]: the square root, the divisions and the rotations run once per environment, not
+//      once per word.  A table without derived slots skips both steps and uses no LDS word;
+//   3. lane c takes the columns c, c + 64, ... of the tensor: it reads the slot, offset and scale of a column ONCE, into
+//      registers, and runs over the E environments: the word of a state or source row comes from global memory (lanes of
+//      neighbouring rows read neighbouring words of a tile, T words apart), a derived one from LDS, and the 64 lanes store
+//      64 consecutive words of the environment's row of `out`.
+// The table is thus read once per wave whatever D is (no LDS copy that would bound D), and the stores of a row are
+// contiguous; the lanes at and beyond D of the last 64 columns idle.  Only environments below N are touched: the padding
+// columns of the last tile are neither read nor turned into rows, and a source is read at rows below its own count only
+// (the host checked every slot), at the tile and column of an environment below N.  The steps of one wave follow each
+// other in program order and LDS serves a wave's accesses in order; the fences keep the compiler from moving them.
+struct ObsSources {
+  const void* ptr[jxs_obs::kSources];
+  int rows[jxs_obs::kSources];
+};
+
+template <typename T, typename O>
+__global__ void __launch_bounds__(256) jxs_env_observe_kernel(const T* __restrict__ state, ObsSources src, const int32_t* __restrict__ codes,
+                                                              const T* __restrict__ offset, const T* __restrict__ scale, int D, unsigned used,
+                                                              jxs_obs::Shape sh, int N, int tile_shift, int env_shift, O* __restrict__ out,
+                                                              long long out_ld) {
+  extern __shared__ __align__(16) unsigned char jxs_observe_lds[];
+  const int lane = threadIdx.x & 63;
+  const int E = 1 << env_shift, tmask = (1 << tile_shift) - 1;
+  const long long env0 = ((long long)blockIdx.x * 4 + (threadIdx.x >> 6)) << env_shift;
+  if (env0 >= N) return;  // (wave-uniform)
+  const int n_env = (long long)N - env0 < E ? (int)(N - env0) : E;
+  T* derived = reinterpret_cast<T*>(jxs_observe_lds) + (size_t)(threadIdx.x >> 6) * (size_t)(jxs_obs::kDerived << env_shift);
+  // word of row `row` of environment env0 + e in a tiled block of `rows` rows (rows * T < 2^30: the host checks)
+  auto word_at = [&](int rows, int row, int e) {
+    const long long env = env0 + e;
+    return (size_t)(env >> tile_shift) * (size_t)(rows << tile_shift) + (size_t)((row << tile_shift) + (int)(env & tmask));
+  };
+  // (the slot of the lane's first column is asked for now: its three loads travel with those of the derived values
+  // instead of starting a further round trip behind them)
+  int32_t code = 0;
+  T off = T(0), sc = T(1);
+  if (lane < D) code = codes[lane], off = offset[lane], sc = scale[lane];
+  if (used != 0) {
+    for (int i = lane; i < (jxs_obs::kDerivedRot << env_shift); i += 64) {
+      const int e = i & (E - 1), k = i >> env_shift;
+      if (((used >> k) & 1u) && e < n_env) {
+        T q[4];
+        for (int j = 0; j < 4; ++j) q[j] = state[word_at(sh.n_rows, jxs_obs::row_quat(sh) + j, e)];
+        derived[i] = jxs_obs::unit_quaternion_component(q, k);
+      }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    for (int i = (jxs_obs::kDerivedRot << env_shift) + lane; i < (jxs_obs::kDerived << env_shift); i += 64) {
+      const int e = i & (E - 1), d = i >> env_shift;
+      if (((used >> d) & 1u) && e < n_env) {
+        T u[4];
+        for (int j = 0; j < 4; ++j) u[j] = (used & 1u) ? derived[(j << env_shift) + e] : T(0);
+        derived[i] = jxs_obs::derived_from_unit<T>(sh, d, u, [&](int r) { return state[word_at(sh.n_rows, r, e)]; });
+      }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  }
+  O* const orow = out + (size_t)env0 * (size_t)out_ld;
+  for (int c = lane; c < D; c += 64) {
+    if (c != lane) code = codes[c], off = offset[c], sc = scale[c];
+    const int kind = jxs_obs::packed_kind(code), index = jxs_obs::packed_index(code), s = jxs_obs::packed_source(code);
+    const bool from_row = kind <= jxs_obs::kSourceRow, from_source = kind == jxs_obs::kSourceRow;
+    const T* base = !from_source ? state : static_cast<const T*>(s == 0 ? src.ptr[0] : s == 1 ? src.ptr[1] : s == 2 ? src.ptr[2] : src.ptr[3]);
+    const int rows = !from_source ? sh.n_rows : (s == 0 ? src.rows[0] : s == 1 ? src.rows[1] : s == 2 ? src.rows[2] : src.rows[3]);
+#pragma unroll 4
+    for (int e = 0; e < n_env; ++e) {
+      const T x = from_row ? base[word_at(rows, index, e)] : derived[(index << env_shift) + e];  // (one load per lane, by its kind)
+      orow[(size_t)e * (size_t)out_ld + c] = (O)jxs_obs::affine(x, off, sc);
+    }
+  }
+}
+
 namespace {
 template <int A, int WB>
 void launch_env_select(const uint8_t* mask, const void* a, const void* b, void* out, int rows, int N, int tile, hipStream_t s) {
@@ -1022,6 +1120,134 @@ int jxs_env_randomize(jxs_model* model, const uint8_t* mask, void* state, int N,
   if (rc != JXS_OK) return rc;
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return hip_fail(e, "jxs_env_randomize");
+  return JXS_OK;
+}
+
+int jxs_observation_create(jxs_model* model, int D, const int32_t* slots, const double* offset, const double* scale,
+                           const int32_t source_rows[4], jxs_observation** out) {
+  if (out == nullptr) return fail(JXS_EINVAL, "null out");
+  *out = nullptr;
+  if (model == nullptr) return fail(JXS_EINVAL, "null model");
+  if (slots == nullptr) return fail(JXS_EINVAL, "null slots");
+  return with_typed(model, [&](auto* mt) -> int {
+    using T = typename std::remove_pointer_t<decltype(mt)>::value_type;
+    const auto& P = mt->pk.P;
+    int bad = -1;
+    const int err = jxs_obs::table_error(slots, D, P.n_rows, source_rows, &bad);
+    if (err == jxs_obs::kBadWidth)
+      return fail(JXS_EINVAL, "jxs_observation_create: D = " + std::to_string(D) + " outside [1, " + std::to_string(JXS_OBS_MAX_WIDTH) + "]");
+    if (err != jxs_obs::kOk) {
+      const char* what = err == jxs_obs::kBadKind ? "unknown kind" : err == jxs_obs::kBadSource ? "source out of range or without rows" : "row or component out of range";
+      return fail(JXS_EINVAL, "jxs_observation_create: slot " + std::to_string(bad) + " {" + std::to_string(slots[3 * bad]) + ", " +
+                                  std::to_string(slots[3 * bad + 1]) + ", " + std::to_string(slots[3 * bad + 2]) + "}: " + what);
+    }
+    auto ob = std::make_unique<jxs_observation>();
+    ob->dtype = model->dtype, ob->D = D, ob->n_rows = P.n_rows, ob->n_joints = P.n;
+    for (int s = 0; s < jxs_obs::kSources; ++s) {
+      ob->source_rows[s] = source_rows != nullptr && source_rows[s] > 0 ? source_rows[s] : 0;
+      if (ob->source_rows[s] >= (1 << 26)) return fail(JXS_EINVAL, "jxs_observation_create: a source of 2^26 rows or more");
+    }
+    if (P.n_rows >= (1 << 26)) return fail(JXS_EINVAL, "jxs_observation_create: a state of 2^26 rows or more");
+    ob->offset_at = ((size_t)D * sizeof(int32_t) + 15) / 16 * 16;
+    ob->scale_at = ob->offset_at + ((size_t)D * sizeof(T) + 15) / 16 * 16;
+    std::vector<unsigned char> host(ob->scale_at + (size_t)D * sizeof(T), 0);
+    int32_t* codes = reinterpret_cast<int32_t*>(host.data());
+    T* off = reinterpret_cast<T*>(host.data() + ob->offset_at);
+    T* sc = reinterpret_cast<T*>(host.data() + ob->scale_at);
+    for (int d = 0; d < D; ++d) {
+      const jxs_obs::Slot s{slots[3 * d], slots[3 * d + 1], slots[3 * d + 2]};
+      const double o = offset != nullptr ? offset[d] : 0.0, c = scale != nullptr ? scale[d] : 1.0;
+      if (!jxs_obs::affine_ok(o, T(0)) || !jxs_obs::affine_ok(c, T(0)))
+        return fail(JXS_EINVAL, "jxs_observation_create: slot " + std::to_string(d) + ": offset or scale not finite in the model's dtype");
+      codes[d] = jxs_obs::pack_slot(s), off[d] = static_cast<T>(o), sc[d] = static_cast<T>(c);
+      if (s.kind == jxs_obs::kSourceRow) ob->sources_used |= 1u << s.source;
+    }
+    for (int r = 0; r < 3; ++r) ob->derived_used[r] = jxs_obs::derived_used(slots, D, r);
+    JXS_HIP(hipMalloc(&ob->table, host.size()));
+    const hipError_t e = hipMemcpy(ob->table, host.data(), host.size(), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+      (void)hipFree(ob->table);
+      return hip_fail(e, "uploading the observation table");
+    }
+    *out = ob.release();
+    return JXS_OK;
+  });
+}
+int jxs_observation_destroy(jxs_observation* observation) {
+  if (observation == nullptr) return JXS_OK;
+  (void)hipFree(observation->table);  // (hipFree waits for the launches that may still read the table)
+  delete observation;
+  return JXS_OK;
+}
+
+int jxs_env_observe(jxs_model* model, const jxs_observation* observation, const void* state, const void* const sources[4], int N,
+                    int velocity_representation, void* out, int out_dtype, int64_t out_ld, void* stream) {
+  if (model == nullptr || observation == nullptr || state == nullptr || out == nullptr) return fail(JXS_EINVAL, "jxs_env_observe: null argument");
+  if (N <= 0) return fail(JXS_EINVAL, "jxs_env_observe: N must be positive");
+  if (velocity_representation != JXS_REPR_INERTIAL && velocity_representation != JXS_REPR_BODY && velocity_representation != JXS_REPR_MIXED)
+    return fail(JXS_EINVAL, "jxs_env_observe: unknown velocity representation");
+  if (out_dtype != JXS_F32 && out_dtype != model->dtype) return fail(JXS_EINVAL, "jxs_env_observe: out_dtype must be JXS_F32 or the model's dtype");
+  const jxs_observation& ob = *observation;
+  if (out_ld < ob.D) return fail(JXS_EINVAL, "jxs_env_observe: out_ld = " + std::to_string(out_ld) + " below D = " + std::to_string(ob.D));
+  ObsSources src{};
+  for (int s = 0; s < jxs_obs::kSources; ++s) {
+    if (!((ob.sources_used >> s) & 1u)) continue;  // (a pointer the table does not use is not looked at)
+    if (sources == nullptr || sources[s] == nullptr) return fail(JXS_EINVAL, "jxs_env_observe: the table reads source " + std::to_string(s) + ", whose pointer is null");
+    src.ptr[s] = sources[s], src.rows[s] = ob.source_rows[s];
+  }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int rc = with_typed(model, [&](auto* mt) {
+    using T = typename std::remove_pointer_t<decltype(mt)>::value_type;
+    const auto& P = mt->pk.P;
+    if (ob.dtype != model->dtype || ob.n_rows != P.n_rows || ob.n_joints != P.n)
+      return fail(JXS_EINVAL, "jxs_env_observe: the observation table was created for another state layout or dtype");
+    const int tile = 64 / mt->pk.G;
+    int tile_shift = 0;
+    while ((1 << tile_shift) < tile) ++tile_shift;
+    if (tile <= 0 || (1 << tile_shift) != tile || tile > 64) return fail(JXS_EINVAL, "jxs_env_observe: the model's tile does not divide the wave");
+    int max_rows = P.n_rows;
+    for (int k = 0; k < jxs_obs::kSources; ++k) max_rows = std::max(max_rows, src.rows[k]);
+    if (jxs_env::tile_words(max_rows, tile) >= (1LL << 30)) return fail(JXS_EINVAL, "jxs_env_observe: rows * tile must be below 2^30");
+    const size_t ob_bytes = out_dtype == JXS_F64 ? 8 : 4;
+    bool aligned = (uintptr_t)state % sizeof(T) == 0 && (uintptr_t)out % ob_bytes == 0;
+    for (int k = 0; k < jxs_obs::kSources; ++k) aligned = aligned && (uintptr_t)src.ptr[k] % sizeof(T) == 0;
+    if (!aligned) return fail(JXS_EINVAL, "jxs_env_observe: state, sources and out must be aligned to their element type");
+    // Environments per wave, E = 2^env_shift with T <= E <= max(T, 32): as many as still leave the chip 8192 waves (256 CUs x
+    // 4 SIMDs x 8), so that the table read and the derived values' prologue are shared by more environments at large N,
+    // while a small batch is spread over as many waves as it has tiles.  Measured on the humanoid (profiles/env_observe.txt):
+    // at N = 65 536 the 60-wide observation is fastest with 8 environments per wave (about 18.5 / 13 / 10.7 / 11.8 / 14.7 us
+    // with 2 / 4 / 8 / 16 / 32), at N = 1024 with one tile per wave (32 environments per wave take twice as long).
+    int knobs, duo_blocks;
+    debug_knobs(knobs, duo_blocks);  // (reads the environment on the first call of the process)
+    (void)knobs, (void)duo_blocks;
+    const int want = g_observe_envs_per_wave.load(std::memory_order_relaxed);
+    int env_shift = tile_shift;
+    const int max_shift = std::max(tile_shift, 5);
+    if (want > 0) {
+      while (env_shift < max_shift && (1 << env_shift) < want) ++env_shift;
+    } else {
+      while (env_shift < max_shift && ((long long)N >> (env_shift + 1)) >= 8192) ++env_shift;
+    }
+    const unsigned used = ob.derived_used[velocity_representation];
+    const size_t lds = used != 0 ? 4 * (size_t)(jxs_obs::kDerived << env_shift) * sizeof(T) : 0;  // (at most 4 * 22 * 64 * 8 = 45 KB)
+    const long long waves = ((long long)N + (1LL << env_shift) - 1) >> env_shift;
+    const dim3 grid((unsigned)((waves + 3) / 4)), block(256);
+    const jxs_obs::Shape sh{P.n_rows, P.n, velocity_representation};
+    const unsigned char* tb = static_cast<const unsigned char*>(ob.table);
+    const int32_t* codes = reinterpret_cast<const int32_t*>(tb);
+    const T* off = reinterpret_cast<const T*>(tb + ob.offset_at);
+    const T* sc = reinterpret_cast<const T*>(tb + ob.scale_at);
+    if (out_dtype == model->dtype)
+      hipLaunchKernelGGL((jxs_env_observe_kernel<T, T>), grid, block, lds, s, static_cast<const T*>(state), src, codes, off, sc, ob.D, used, sh, N,
+                         tile_shift, env_shift, static_cast<T*>(out), (long long)out_ld);
+    else
+      hipLaunchKernelGGL((jxs_env_observe_kernel<T, float>), grid, block, lds, s, static_cast<const T*>(state), src, codes, off, sc, ob.D, used, sh, N,
+                         tile_shift, env_shift, static_cast<float*>(out), (long long)out_ld);
+    return (int)JXS_OK;
+  });
+  if (rc != JXS_OK) return rc;
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(e, "jxs_env_observe");
   return JXS_OK;
 }
 

@@ -517,6 +517,64 @@ class JaxSimModelData:
         """Bit 0 of ``env_flags()`` as a host bool array: which environments hold a NaN or an infinity."""
         return self._out((self.env_flags().to_host() & 1) != 0)
 
+    def observe(self, spec: "ObservationSpec", out=None, sources: dict | None = None):
+        """The input of a policy, an environment-major ``(batch_size, spec.size)`` matrix on the device, assembled by one
+        kernel (``jxs_env_observe``) on the current stream -- what the reference's user writes as ``jnp.concatenate`` of
+        ``data.joint_positions``, ``data.base_orientation``, ``data.base_velocity`` ... under ``vmap``: no download, no
+        synchronisation.
+
+        ``sources``: ``{name: DeviceArray}`` for every source the spec names, each ``[rows][batch_size]`` of this object's
+        dtype and tile (what ``centroidal_quantities(out=)``, ``frame.kinematics(out=)``, ``gravity_compensation_torques``
+        return, or last step's torques).  ``out=None`` returns a new ``runtime.DeviceMatrix`` of ``spec.out_dtype``; a
+        ``DeviceMatrix`` or any object with a 2-D ``__cuda_array_interface__`` of shape ``(batch_size, spec.size)``, typestr
+        float32 or this object's dtype and strides ``None`` or ``(ld * itemsize, itemsize)``, ``ld >= spec.size``, is
+        written in place (zero copy; only the ``spec.size`` columns of each row) and returned.  The base velocity is
+        expressed in ``spec.velocity_representation``, or in this object's representation at the call if that is ``None``.
+        ``ValueError`` before any launch for a spec of another layout or dtype, a missing, unknown or mis-shaped source, a
+        wrong ``out``."""
+        from .api.model import _device_model_fast
+
+        if not isinstance(spec, ObservationSpec):
+            raise ValueError(f"spec must be an ObservationSpec, not {type(spec).__name__}")
+        st = self._state
+        if spec.layout != StateLayout.of(self._model_ref) or spec.layout.n_rows != st.rows:
+            raise ValueError(f"spec was built for another model layout ({spec.layout} != {StateLayout.of(self._model_ref)})")
+        if spec.dtype != self.dtype:
+            raise ValueError(f"spec was built for dtype {spec.dtype}, not {self.dtype}")
+        sources = dict(sources or {})
+        unknown = sorted(set(sources) - set(spec.source_names))
+        if unknown:
+            raise ValueError(f"sources {unknown} are not named by the spec (it names {list(spec.source_names)})")
+        blocks = []
+        for name, rows in zip(spec.source_names, spec.source_rows):
+            blk = sources.get(name)
+            if blk is None:
+                raise ValueError(f"the spec reads the source {name!r}, which was not given")
+            if not isinstance(blk, runtime.DeviceArray):
+                raise ValueError(f"source {name!r} must be a runtime.DeviceArray, not {type(blk).__name__}")
+            if blk.shape != (rows, st.cols) or blk.dtype != st.dtype or blk.tile != st.tile:
+                raise ValueError(f"source {name!r} is {blk.shape} {blk.dtype} tile {blk.tile}: expected ({rows}, {st.cols}) {st.dtype} tile {st.tile}")
+            blocks.append(blk)
+        N, D = st.cols, spec.size
+        if out is None:
+            out = runtime.DeviceMatrix(N, D, spec.out_dtype)
+        if isinstance(out, runtime.DeviceMatrix):
+            if out.shape != (N, D) or out.dtype not in (np.dtype(np.float32), st.dtype):
+                raise ValueError(f"out is {out.shape} {out.dtype}: expected ({N}, {D}) float32 or {st.dtype}")
+            optr, ld, odt = out.ptr, D, out.dtype
+        elif hasattr(out, "__cuda_array_interface__"):
+            optr, ld, odt = runtime.foreign_matrix(out, N, D, tuple({"<f4", st.dtype.str}))
+        else:
+            raise ValueError(f"out must be None, a runtime.DeviceMatrix or a 2-D __cuda_array_interface__ object, not {type(out).__name__}")
+        rep = self.velocity_representation if spec.velocity_representation is None else spec.velocity_representation
+        dm = _device_model_fast(self._model_ref, self.dtype)
+        ptrs = (C.c_void_p * 4)(*[b.ptr for b in blocks])
+        _lib.check(
+            _lib.load().jxs_env_observe(dm.handle, spec._table(dm), st.ptr, ptrs, N, int(rep), optr, _lib.dtype_code(odt), ld, runtime._sp()),
+            "jxs_env_observe",
+        )
+        return out
+
 
 def random_model_data(
     model,
@@ -680,3 +738,167 @@ def random_model_data_device(
     state = runtime.DeviceArray(dist.layout.n_rows, int(batch_size), dist.dtype, tile=tile, zero=int(batch_size) % tile != 0)
     data = JaxSimModelData(model, state, dist.velocity_representation, True)
     return data.reset_random_where(None, dist, seed=seed, draw=draw, first_env=first_env, inplace=True)
+
+
+# kinds of an observation slot (JXS_OBS_* of include/jaxsim_amd.h)
+OBS_STATE_ROW, OBS_SOURCE_ROW, OBS_BASE_QUAT_UNIT, OBS_BASE_ROTATION, OBS_BASE_VELOCITY, OBS_PROJECTED_GRAVITY = range(6)
+OBS_MAX_WIDTH, OBS_MAX_SOURCES = 4096, 4
+
+
+class ObservationSpec:
+    """What ``JaxSimModelData.observe`` assembles for one model: an ordered list of terms, flattened into ``size`` slots
+    ``(kind, source, index)`` with an offset and a scale each (the table of ``jxs_observation_create``).  Built once on the
+    host -- no device is needed --, uploaded at the first ``observe``, used for every step of a loop.
+
+    ``slots`` ``[size, 3]`` int32, ``offset`` / ``scale`` ``[size]`` float64, ``slices``: term key -> column slice,
+    ``source_names`` / ``source_rows``: the auxiliary blocks ``observe`` must be given, in source order."""
+
+    def __init__(self, layout: StateLayout, dtype, out_dtype, velocity_representation, slots, offset, scale, slices, source_names, source_rows):
+        self.layout = layout
+        self.dtype = np.dtype(dtype)
+        self.out_dtype = np.dtype(out_dtype)
+        self.velocity_representation = None if velocity_representation is None else VelRepr(velocity_representation)
+        self.slots = np.ascontiguousarray(slots, dtype=np.int32).reshape(-1, 3)
+        self.offset = np.ascontiguousarray(offset, dtype=np.float64)
+        self.scale = np.ascontiguousarray(scale, dtype=np.float64)
+        self.slices = dict(slices)
+        self.source_names, self.source_rows = tuple(source_names), tuple(int(r) for r in source_rows)
+        self._handle = None
+
+    @property
+    def size(self) -> int:
+        return self.slots.shape[0]
+
+    @staticmethod
+    def build(model, terms, *, dtype=np.float32, velocity_representation=None, out_dtype=None) -> "ObservationSpec":
+        """``terms``: an ordered sequence of names or ``(name, options)``:
+
+        * ``"joint_positions"``, ``"joint_velocities"`` -- option ``joints=[names]`` picks and orders a subset;
+        * ``"base_position"``, ``"base_height"``, ``"base_quaternion"`` (as stored), ``"base_orientation"`` (unit norm, the
+          rule of ``data.base_orientation``), ``"base_rotation"`` (row-major);
+        * ``"base_velocity"``, ``"base_linear_velocity"``, ``"base_angular_velocity"`` (in ``velocity_representation``; ``None``
+          = the data object's at the call), ``"projected_gravity"`` (``R^T (0, 0, -1)``), ``"tangential_deformation"``;
+        * ``("source", dict(name=..., rows=...))``: an auxiliary block of ``rows`` rows handed to ``observe`` under that
+          name (at most four different ones); option ``take=[row indices]`` picks rows, the default is all of them.
+
+        Every term takes ``scale`` and ``offset`` (a scalar or one value per element, for instance the default pose): the
+        element is ``(x - offset) * scale``.  A term is found in ``slices`` under its name (a source under its source
+        name), or under the option ``key``.  ``out_dtype``: float32 or ``dtype`` (the default).  ``ValueError`` for an
+        unknown term, option or joint, a key used twice, a row out of range, a value that is not finite in ``dtype``, more
+        than four sources, no element at all or more than 4096."""
+        lay = StateLayout.of(model)
+        dt = np.dtype(dtype)
+        _lib.dtype_code(dt)
+        odt = dt if out_dtype is None else np.dtype(out_dtype)
+        if odt not in (np.dtype(np.float32), dt):
+            raise ValueError(f"out_dtype {odt}: expected float32 or {dt}")
+        if velocity_representation is not None:
+            velocity_representation = VelRepr(velocity_representation)
+        n = lay.n_joints
+        state = lambda first, count: [(OBS_STATE_ROW, 0, first + k) for k in range(count)]  # noqa: E731
+        kind = lambda k, comps: [(k, 0, c) for c in comps]  # noqa: E731
+        fixed = {
+            "base_position": state(lay.row_pos, 3),
+            "base_height": state(lay.row_pos + 2, 1),
+            "base_quaternion": state(lay.row_quat, 4),
+            "base_orientation": kind(OBS_BASE_QUAT_UNIT, range(4)),
+            "base_rotation": kind(OBS_BASE_ROTATION, range(9)),
+            "base_velocity": kind(OBS_BASE_VELOCITY, range(6)),
+            "base_linear_velocity": kind(OBS_BASE_VELOCITY, range(3)),
+            "base_angular_velocity": kind(OBS_BASE_VELOCITY, range(3, 6)),
+            "projected_gravity": kind(OBS_PROJECTED_GRAVITY, range(3)),
+            "tangential_deformation": state(lay.row_m, 3 * lay.n_points),
+        }
+        slots, offset, scale, slices, src_names, src_rows = [], [], [], {}, [], []
+        if isinstance(terms, (str, bytes)):
+            raise ValueError("terms must be a sequence of names or (name, options), not one string")
+        for term in terms:
+            if isinstance(term, str):
+                name, opts = term, {}
+            elif isinstance(term, (tuple, list)) and len(term) == 2 and isinstance(term[0], str) and isinstance(term[1], dict):
+                name, opts = term[0], dict(term[1])
+            else:
+                raise ValueError(f"term {term!r}: expected a name or (name, options)")
+            key = opts.pop("key", None)
+            t_scale, t_offset = opts.pop("scale", 1.0), opts.pop("offset", 0.0)
+            if name in ("joint_positions", "joint_velocities"):
+                first = lay.row_s if name == "joint_positions" else lay.row_sd
+                joints = opts.pop("joints", None)
+                if joints is None:
+                    idx = list(range(n))
+                else:
+                    known = {nm: i for i, nm in enumerate(model.joint_names())}
+                    missing = [j for j in joints if j not in known]
+                    if missing:
+                        raise ValueError(f"term {name!r}: unknown joints {missing}")
+                    idx = [known[j] for j in joints]
+                mine = [(OBS_STATE_ROW, 0, first + i) for i in idx]
+            elif name == "source":
+                sname, rows = opts.pop("name", None), opts.pop("rows", None)
+                if not isinstance(sname, str) or not isinstance(rows, (int, np.integer)) or rows <= 0:
+                    raise ValueError(f"term {term!r}: a source needs name=<str> and rows=<positive int>")
+                take = opts.pop("take", None)
+                take = list(range(int(rows))) if take is None else [int(r) for r in take]
+                if any(r < 0 or r >= rows for r in take):
+                    raise ValueError(f"source {sname!r}: rows {take} outside [0, {rows})")
+                if sname in src_names:
+                    if src_rows[src_names.index(sname)] != int(rows):
+                        raise ValueError(f"source {sname!r} named with {rows} and with {src_rows[src_names.index(sname)]} rows")
+                else:
+                    if len(src_names) == OBS_MAX_SOURCES:
+                        raise ValueError(f"more than {OBS_MAX_SOURCES} sources")
+                    src_names.append(sname)
+                    src_rows.append(int(rows))
+                mine = [(OBS_SOURCE_ROW, src_names.index(sname), r) for r in take]
+                key = sname if key is None else key
+            elif name in fixed:
+                mine = fixed[name]
+            else:
+                raise ValueError(f"unknown observation term {name!r}")
+            if opts:
+                raise ValueError(f"term {name!r}: unknown options {sorted(opts)}")
+            key = name if key is None else key
+            if key in slices:
+                raise ValueError(f"two terms under the key {key!r}: give one of them the option key=")
+            vals = []
+            for what, v in (("scale", t_scale), ("offset", t_offset)):
+                a = np.asarray(v, dtype=np.float64)
+                if a.ndim > 1 or (a.ndim == 1 and a.shape[0] != len(mine)):
+                    raise ValueError(f"term {name!r}: {what} of shape {a.shape}: expected a scalar or {len(mine)} values")
+                a = np.broadcast_to(a, (len(mine),))
+                with np.errstate(over="ignore"):
+                    if not (np.isfinite(a).all() and np.isfinite(a.astype(dt)).all()):
+                        raise ValueError(f"term {name!r}: {what} is not finite in {dt.name}")
+                vals.append(a)
+            slices[key] = slice(len(slots), len(slots) + len(mine))
+            slots += mine
+            scale += list(vals[0])
+            offset += list(vals[1])
+        if not 1 <= len(slots) <= OBS_MAX_WIDTH:
+            raise ValueError(f"an observation of {len(slots)} elements: expected 1 .. {OBS_MAX_WIDTH}")
+        return ObservationSpec(lay, dt, odt, velocity_representation, slots, offset, scale, slices, src_names, src_rows)
+
+    def _table(self, dm) -> C.c_void_p:
+        """The device table (``jxs_observation``), uploaded at the first use: one small allocation and a blocking copy.  The
+        library checks it against the layout and dtype of the model of every launch, so one table serves every device
+        model of this spec's layout."""
+        if self._handle is None:
+            h = C.c_void_p()
+            rows = (C.c_int32 * 4)(*(list(self.source_rows) + [0] * (4 - len(self.source_rows))))
+            _lib.check(
+                _lib.load().jxs_observation_create(
+                    dm.handle, self.size, self.slots.ctypes.data_as(C.POINTER(C.c_int32)), self.offset.ctypes.data_as(C.POINTER(C.c_double)),
+                    self.scale.ctypes.data_as(C.POINTER(C.c_double)), rows, C.byref(h)),
+                "jxs_observation_create",
+            )  # fmt: skip
+            self._handle = h
+        return self._handle
+
+    def __del__(self):
+        h = getattr(self, "_handle", None)
+        if h is not None:
+            self._handle = None
+            try:
+                _lib.load().jxs_observation_destroy(h)
+            except Exception:
+                pass

@@ -400,6 +400,64 @@ def foreign_vector(obj, n: int | None, typestrs: tuple) -> tuple[int, int]:
     return int(ptr), int(shape[0])
 
 
+class DeviceMatrix:
+    """An environment-major ``(n, width)`` device matrix of float32/float64, row-major and contiguous: what
+    ``JaxSimModelData.observe`` returns.  Pool-backed like ``DeviceArray`` (its storage is one of one row and tile 1); its
+    ``__cuda_array_interface__`` has the shape ``(n, width)``, so another framework reads it in place."""
+
+    def __init__(self, n: int, width: int, dtype):
+        self.n, self.width = int(n), int(width)
+        if self.n <= 0 or self.width <= 0:
+            raise ValueError("a device matrix needs at least one row and one column")
+        self._buf = DeviceArray(1, self.n * self.width, dtype, tile=1)
+
+    @property
+    def ptr(self):
+        return self._buf.ptr
+
+    @property
+    def shape(self):
+        return (self.n, self.width)
+
+    @property
+    def dtype(self):
+        return self._buf.dtype
+
+    @property
+    def __cuda_array_interface__(self) -> dict:
+        return {"shape": self.shape, "typestr": self.dtype.str, "data": (int(self.ptr), False), "strides": None, "version": 3}
+
+    def to_host(self) -> np.ndarray:
+        return self._buf.to_host_raw().reshape(self.n, self.width)
+
+
+def foreign_matrix(obj, n: int, width: int, typestrs: tuple) -> tuple[int, int, np.dtype]:
+    """``(device pointer, leading dimension in elements, dtype)`` of an object that speaks ``__cuda_array_interface__``,
+    used with ZERO copy as an environment-major ``(n, width)`` matrix: 2-D, of that shape, of one of ``typestrs``, its
+    strides ``None`` or ``(ld * itemsize, itemsize)`` with ``ld >= width``; ``ValueError`` otherwise.  The caller keeps
+    ``obj`` alive and orders the stream that reads it behind the current one."""
+    cai = obj.__cuda_array_interface__
+    shape = tuple(cai["shape"])
+    if shape != (n, width):
+        raise ValueError(f"device array of shape {shape}: expected ({n}, {width})")
+    if cai["typestr"] not in typestrs:
+        raise ValueError(f"device array of typestr {cai['typestr']!r}: expected one of {typestrs}")
+    dt = np.dtype(cai["typestr"])
+    ld = width
+    strides = cai.get("strides")
+    if strides is not None:
+        strides = tuple(strides)
+        if len(strides) != 2 or strides[1] != dt.itemsize or strides[0] % dt.itemsize != 0 or strides[0] < width * dt.itemsize:
+            raise ValueError(f"device array with strides {strides}: expected (ld * {dt.itemsize}, {dt.itemsize}) with ld >= {width}")
+        ld = strides[0] // dt.itemsize
+    ptr = cai["data"][0]
+    if not ptr:
+        raise ValueError("device array with a null pointer")
+    if cai["data"][1]:
+        raise ValueError("device array is read-only")
+    return int(ptr), int(ld), dt
+
+
 MASK_TYPESTRS = ("|b1", "|u1")
 INDEX_TYPESTRS = ("<i4",)
 
