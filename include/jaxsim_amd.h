@@ -368,6 +368,45 @@ int jxs_env_observe(jxs_model* model, const jxs_observation* observation, const 
                     const void* const sources[4], int N, int velocity_representation, void* out, int out_dtype,
                     int64_t out_ld, void* stream);
 
+/* jxs_env_act: the joint torques of a policy's action, the tiled [n][N] block `out_tau` that jxs_step reads as `tau`,
+ *   computed on the device from the environment-major action tensor `actions` = [N][act_ld] and the joint positions and
+ *   velocities of the tiled state block -- what the reference's user writes as the controller that a `jax.lax.scan` of
+ *   `step` carries under `vmap`: scaled position or velocity targets turned into torques by a PD law at the physics rate,
+ *   from the q and qdot of every sub-step between two policy evaluations.
+ *   The law is described once per model by an immutable table of n entries, one per joint in the order of the state's
+ *   joint rows: `joints` [n][2] = {mode, column} and `params` [n][8] = {scale, offset, kp, kd, action_clip, target_lo,
+ *   target_hi, torque_limit} (rounded to the model's dtype).  With clamp(x, lo, hi) = x < lo ? lo : (hi < x ? hi : x) --
+ *   a NaN x passes through -- the word of joint j of environment e is, every operation rounded in the model's dtype:
+ *     a   = column < 0 ? 0 : actions[e][column]
+ *     u   = clamp(a, -action_clip, action_clip) * scale + offset
+ *     t   = JXS_ACT_OFF       0
+ *           JXS_ACT_TORQUE    u
+ *           JXS_ACT_POSITION  kp * (clamp(u, target_lo, target_hi) - q_j) - kd * qdot_j
+ *           JXS_ACT_VELOCITY  kd * (u - qdot_j)
+ *     t   = feed_forward ? t + feed_forward[j][e] : t
+ *     tau = clamp(t, -torque_limit, torque_limit)
+ *   JXS_ACT_POSITION with column -1 holds `offset`.  `feed_forward` is NULL or a tiled [n][N] block of the model's dtype
+ *   and tile (what jxs_gravity_torques writes).
+ *   jxs_action_create refuses with JXS_EINVAL: a model without joints, A outside [0, JXS_ACT_MAX_WIDTH], an unknown mode, a
+ *   column outside [-1, A), a scale, offset, kp or kd that is not finite in the model's dtype, an action_clip or
+ *   torque_limit that is negative, NaN or finite but not in the model's dtype (+inf: no limit), target_lo > target_hi or
+ *   NaN (infinities allowed).  A table may be used with every model of the same state layout and dtype.
+ *   jxs_env_act: `act_ld` >= A; `act_dtype` is JXS_F32 or the model's dtype; `actions` may be NULL exactly when no joint
+ *   has a column.  Every word of `out_tau` of an environment < N is written, the padding columns of the last tile are
+ *   written as zero, nothing else is written.  Action columns the table does not name and the gap A .. act_ld-1 may hold
+ *   anything; no action row at or beyond N is read; padding columns of the state and of `feed_forward` never reach a
+ *   word of a real environment.  Asynchronous on `stream`; no allocation, synchronisation, memset or host read (legal
+ *   between two jxs_step launches).  JXS_EINVAL: a null model, table, state or out_tau, N <= 0, act_ld < A, an unknown
+ *   act_dtype, NULL actions while a column is used, a table of another layout or dtype, a misaligned block.            */
+#define JXS_ACT_MAX_WIDTH 4096
+enum { JXS_ACT_OFF = 0, JXS_ACT_TORQUE = 1, JXS_ACT_POSITION = 2, JXS_ACT_VELOCITY = 3 };
+typedef struct jxs_action jxs_action;
+int jxs_action_create(jxs_model* model, int A, const int32_t* joints /* [n][2] = mode, column */,
+                      const double* params /* [n][8] */, jxs_action** out);
+int jxs_action_destroy(jxs_action* action);
+int jxs_env_act(jxs_model* model, const jxs_action* action, const void* state, const void* actions, int act_dtype,
+                int64_t act_ld, const void* feed_forward, void* out_tau, int N, void* stream);
+
 /* RigidContacts only.  A contact-force QP or an impact solve whose result is not finite (fp32 on a numerically
  * singular stance) is DISCARDED -- that environment takes the step without contact forces / without the
  * velocity reset instead of poisoning its state -- where the reference would propagate NaN

@@ -246,6 +246,9 @@ def _declare(lib):
         "jxs_observation_create": [vp, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(vp)],
         "jxs_observation_destroy": [vp],
         "jxs_env_observe": [vp, vp, vp, C.POINTER(vp), C.c_int, C.c_int, vp, C.c_int, C.c_int64, vp],
+        "jxs_action_create": [vp, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(vp)],
+        "jxs_action_destroy": [vp],
+        "jxs_env_act": [vp, vp, vp, vp, C.c_int, C.c_int64, vp, vp, C.c_int, vp],
         "jxs_step_repeat": [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp],
         "jxs_step_repeat_timed": [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, C.POINTER(C.c_double)],
         "jxs_refresh_kinematics": [vp, vp, vp, vp, C.c_int, vp],

@@ -1,6 +1,7 @@
 """``jaxsim.api.data`` mirror (``src/jaxsim/api/data.py``)."""
 
 from ..data import (  # noqa: F401
+    ActionSpec,
     JaxSimModelData,
     ObservationSpec,
     RandomStateDistribution,

@@ -235,6 +235,29 @@ def step(
     return JaxSimModelData(model, out, data.velocity_representation, data._batched)
 
 
+def control_steps(model: JaxSimModel, data: JaxSimModelData, spec, actions, n_substeps: int, *, feed_forward=None,
+                  inplace: bool = True) -> JaxSimModelData:  # fmt: skip
+    """``n_substeps`` physics steps under one policy action (extension): the decimation loop of a learning environment, two
+    launches per sub-step -- ``data.act(spec, actions)`` reads the CURRENT joint positions and velocities and writes the
+    torques, ``step`` consumes them -- so that the PD law runs at the physics rate.  Everything is enqueued on the current
+    stream; nothing synchronises.  ``actions`` as for ``JaxSimModelData.act`` (a host array is uploaded once);
+    ``feed_forward`` is the same block for every sub-step.  ``inplace=True`` advances ``data``'s buffer; ``inplace=False``
+    leaves ``data`` untouched and returns a new object."""
+    if int(n_substeps) < 1:
+        raise ValueError("n_substeps must be at least 1")
+    from ..data import ActionSpec
+
+    if not isinstance(spec, ActionSpec):
+        raise ValueError(f"spec must be an ActionSpec, not {type(spec).__name__}")
+    if actions is not None and not isinstance(actions, runtime.DeviceMatrix) and not hasattr(actions, "__cuda_array_interface__"):
+        actions = data._action_tensor(spec, actions)[0]  # (the uploaded matrix)
+    tau = None
+    for k in range(int(n_substeps)):
+        tau = data.act(spec, actions, feed_forward=feed_forward, out=tau)
+        data = step(model, data, joint_force_references=tau, inplace=inplace or k > 0)
+    return data
+
+
 def rollout(model: JaxSimModel, data: JaxSimModelData, n_steps: int, *, link_forces=None,
             joint_force_references=None, return_trajectory: bool = False):  # fmt: skip
     """``n_steps`` back-to-back steps (what ``jax.lax.fori_loop`` / ``jax.lax.scan`` over ``step`` does in the

@@ -23,6 +23,7 @@
 #include <type_traits>
 
 #include "../../include/jaxsim_amd.h"
+#include "jxs_env_act.h"
 #include "jxs_env_observe.h"
 #include "jxs_env_ops.h"
 #include "jxs_env_random.h"
@@ -52,9 +53,12 @@ namespace {
 // tests switch variants between launches of one process.  Launches captured in a hipGraph keep what they captured.
 std::atomic<int> g_knobs{-1}, g_duo_max_blocks{0};
 std::atomic<int> g_observe_envs_per_wave{0};  // JXS_OBSERVE_ENVS_PER_WAVE: 0 = the launcher's own rule (tools/bench_env_observe.py)
+std::atomic<int> g_act_envs_per_wave{0};  // JXS_ACT_ENVS_PER_WAVE: 0 = the launcher's own rule (tools/bench_env_act.py)
 void load_knobs() {
   const char* ow = std::getenv("JXS_OBSERVE_ENVS_PER_WAVE");
   g_observe_envs_per_wave.store(ow == nullptr ? 0 : std::atoi(ow));
+  const char* aw = std::getenv("JXS_ACT_ENVS_PER_WAVE");
+  g_act_envs_per_wave.store(aw == nullptr ? 0 : std::atoi(aw));
   auto on = [](const char* name) { const char* v = std::getenv(name); return v != nullptr && std::atoi(v) != 0; };
   int k = 0;
   if (on("JXS_NO_MFMA")) k |= jxs::KNOB_NO_MFMA;
@@ -175,6 +179,16 @@ struct jxs_observation {
   unsigned derived_used[3] = {0, 0, 0};  // per JXS_REPR_*: the derived values a launch computes (jxs_obs::derived_used)
   void* table = nullptr;             // device
   size_t offset_at = 0, scale_at = 0;  // bytes from `table`
+};
+
+// an immutable action table on the device (jxs_action_create): per joint its packed word (jxs_act::pack_joint) and its
+// eight parameters (jxs_act::Params), in one allocation [codes | params]
+struct jxs_action {
+  int dtype = JXS_F32;
+  int A = 0, n_rows = 0, n_joints = 0;
+  bool reads_actions = false;  // some joint has a column
+  void* table = nullptr;       // device
+  size_t params_at = 0;        // bytes from `table`
 };
 
 struct jxs_model {
@@ -764,12 +778,94 @@ __global__ void __launch_bounds__(256) jxs_env_observe_kernel(const T* __restric
   }
 }
 
+// The joint torques out[n][N] (tiled) of a policy's action tensor actions[N][act_ld] (the arithmetic is jxs_env_act.h:
+// every word is jxs_act::torque_word of its joint and its environment).  A wave takes E = 2^env_shift consecutive
+// environments -- whole tiles, E >= T --, four waves per workgroup that share nothing.  Its lanes run over the words of its
+// tiles of `out` in accesses of AB bytes (the widest the tile spans and the block addresses allow, jxs_env::access_bytes).
+// Word w = j T + c of a tile belongs to joint j and column c, and the q rows (state rows 7 ..), the qd rows (13 + n ..),
+// feed_forward and out are each one contiguous span of n T words per tile, so the same access index serves all four.  The
+// action tensor is the one transposed operand: a lane gathers actions[e][column_j], so neighbouring lanes read words act_ld
+// apart -- but the E rows of a wave are one short stretch of memory whose lines the wave uses whole, and staging them
+// through LDS first measured slower (profiles/env_act_both_reads.txt).  The joint's packed word and
+// its eight parameters are read by joint index; the T lanes of a joint read the same record.
+// Only action rows below N are read.  The padding columns of the last tile are read from the state and from feed_forward
+// with the access they share with real columns, never used, and written as zero.
+template <typename T, typename AT, int AB>
+__global__ void __launch_bounds__(256) jxs_env_act_kernel(const T* __restrict__ state, const AT* __restrict__ actions, long long act_ld,
+                                                          const int32_t* __restrict__ codes, const jxs_act::Params<T>* __restrict__ params,
+                                                          const T* __restrict__ ff, T* __restrict__ out, int n, int n_rows, int N,
+                                                          int tile_shift, int env_shift) {
+  constexpr int WB = sizeof(T), WPA = AB / WB;  // bytes per word, words per access
+  const int lane = threadIdx.x & 63;
+  const int E = 1 << env_shift, tile = 1 << tile_shift, tmask = tile - 1;
+  const long long env0 = ((long long)blockIdx.x * 4 + (threadIdx.x >> 6)) << env_shift;
+  if (env0 >= N) return;  // (wave-uniform)
+  const int n_env = (long long)N - env0 < E ? (int)(N - env0) : E;
+  const int n_tiles = (n_env + tmask) >> tile_shift;
+  const AT* const arow = actions == nullptr ? nullptr : actions + (size_t)env0 * (size_t)act_ld;
+  const int span = n << tile_shift;  // words of the joints of one tile (n * T < 2^30: the host checks)
+  const unsigned per_tile = (unsigned)(span / WPA);  // (the host chose AB so that this is exact)
+  const size_t tile0 = (size_t)(env0 >> tile_shift);
+  const unsigned char* const qp = reinterpret_cast<const unsigned char*>(state + tile0 * ((size_t)n_rows << tile_shift) + ((size_t)jxs_act::row_q(n) << tile_shift));
+  const size_t qd_at = (size_t)((jxs_act::row_qd(n) - jxs_act::row_q(n)) << tile_shift) * WB;  // bytes from a tile's q rows to its qd rows
+  const size_t state_tile = ((size_t)n_rows << tile_shift) * WB;
+  const unsigned char* const fp = ff == nullptr ? nullptr : reinterpret_cast<const unsigned char*>(ff + tile0 * (size_t)span);
+  unsigned char* const op = reinterpret_cast<unsigned char*>(out + tile0 * (size_t)span);
+  for (unsigned i = lane; i < (unsigned)n_tiles * per_tile; i += 64) {
+    const unsigned tl = i / per_tile, r = i - tl * per_tile;  // tile of the wave, access inside the tile's span
+    const unsigned char* const qa = qp + (size_t)tl * state_tile + (size_t)r * AB;
+    const EnvPack<AB> vq = *reinterpret_cast<const EnvPack<AB>*>(qa);
+    const EnvPack<AB> vqd = *reinterpret_cast<const EnvPack<AB>*>(qa + qd_at);
+    EnvPack<AB> vff{}, v;
+    if (fp != nullptr) vff = *reinterpret_cast<const EnvPack<AB>*>(fp + (size_t)i * AB);
+#pragma unroll
+    for (int k = 0; k < WPA; ++k) {
+      const int w = (int)r * WPA + k, j = w >> tile_shift;
+      const int e = (int)(tl << tile_shift) + (w & tmask);
+      T t = T(0);
+      if (e < n_env) {
+        const int32_t code = codes[j];
+        const jxs_act::Params<T> p = params[j];
+        const int column = jxs_act::packed_column(code);
+        T a = T(0);
+        if (column >= 0) a = (T)arow[(size_t)e * (size_t)act_ld + column];
+        T q, qd, f = T(0);
+        __builtin_memcpy(&q, &vq.u[k * (WB / 4)], WB);
+        __builtin_memcpy(&qd, &vqd.u[k * (WB / 4)], WB);
+        if (fp != nullptr) __builtin_memcpy(&f, &vff.u[k * (WB / 4)], WB);
+        t = jxs_act::torque_word(jxs_act::packed_mode(code), column, a, p.v, q, qd, fp != nullptr, f);
+      }
+      __builtin_memcpy(&v.u[k * (WB / 4)], &t, WB);
+    }
+    *reinterpret_cast<EnvPack<AB>*>(op + (size_t)i * AB) = v;
+  }
+}
+
 namespace {
 template <int A, int WB>
 void launch_env_select(const uint8_t* mask, const void* a, const void* b, void* out, int rows, int N, int tile, hipStream_t s) {
   const long long tiles = jxs_env::n_tiles(N, tile);
   hipLaunchKernelGGL((jxs_env_select_kernel<A, WB>), dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, s, mask, (const unsigned char*)a,
                      (const unsigned char*)b, (unsigned char*)out, rows, N, tile, tiles);
+}
+
+template <typename T, typename AT>
+void launch_env_act(int access, dim3 grid, hipStream_t s, const void* state, const void* actions, long long act_ld, const jxs_action& ac,
+                    const void* ff, void* out, int N, int tile_shift, int env_shift) {
+  const unsigned char* tb = static_cast<const unsigned char*>(ac.table);
+  const int32_t* codes = reinterpret_cast<const int32_t*>(tb);
+  const jxs_act::Params<T>* params = reinterpret_cast<const jxs_act::Params<T>*>(tb + ac.params_at);
+#define JXS_ACT_LAUNCH(AB)                                                                                                                    \
+  hipLaunchKernelGGL((jxs_env_act_kernel<T, AT, AB>), grid, dim3(256), 0, s, static_cast<const T*>(state), static_cast<const AT*>(actions), act_ld, \
+                     codes, params, static_cast<const T*>(ff), static_cast<T*>(out), ac.n_joints, ac.n_rows, N, tile_shift, env_shift)
+  if (access == 16) {
+    JXS_ACT_LAUNCH(16);
+  } else if (access == 8) {
+    JXS_ACT_LAUNCH(8);
+  } else if constexpr (sizeof(T) == 4) {
+    JXS_ACT_LAUNCH(4);
+  }
+#undef JXS_ACT_LAUNCH
 }
 
 template <typename T>
@@ -1248,6 +1344,116 @@ int jxs_env_observe(jxs_model* model, const jxs_observation* observation, const 
   if (rc != JXS_OK) return rc;
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return hip_fail(e, "jxs_env_observe");
+  return JXS_OK;
+}
+
+int jxs_action_create(jxs_model* model, int A, const int32_t* joints, const double* params, jxs_action** out) {
+  if (out == nullptr) return fail(JXS_EINVAL, "null out");
+  *out = nullptr;
+  if (model == nullptr) return fail(JXS_EINVAL, "null model");
+  if (joints == nullptr || params == nullptr) return fail(JXS_EINVAL, "jxs_action_create: null joints or params");
+  return with_typed(model, [&](auto* mt) -> int {
+    using T = typename std::remove_pointer_t<decltype(mt)>::value_type;
+    const auto& P = mt->pk.P;
+    const int n = P.n;
+    if (n < 1) return fail(JXS_EINVAL, "jxs_action_create: the model has no joints");
+    int bad = -1;
+    const int err = jxs_act::table_error(joints, params, n, A, T(0), &bad);
+    if (err == jxs_act::kBadWidth)
+      return fail(JXS_EINVAL, "jxs_action_create: A = " + std::to_string(A) + " outside [0, " + std::to_string(JXS_ACT_MAX_WIDTH) + "]");
+    if (err != jxs_act::kOk) {
+      const char* what = err == jxs_act::kBadMode     ? "unknown mode"
+                         : err == jxs_act::kBadColumn ? "column outside [-1, A)"
+                         : err == jxs_act::kNotFinite ? "scale, offset, kp or kd not finite in the model's dtype"
+                         : err == jxs_act::kBadLimit  ? "action_clip or torque_limit negative, NaN or not finite in the model's dtype"
+                                                      : "target_lo above target_hi, NaN or not finite in the model's dtype";
+      return fail(JXS_EINVAL, "jxs_action_create: joint " + std::to_string(bad) + " {" + std::to_string(joints[2 * bad]) + ", " +
+                                  std::to_string(joints[2 * bad + 1]) + "}: " + what);
+    }
+    if (P.n_rows >= (1 << 26)) return fail(JXS_EINVAL, "jxs_action_create: a state of 2^26 rows or more");
+    auto ac = std::make_unique<jxs_action>();
+    ac->dtype = model->dtype, ac->A = A, ac->n_rows = P.n_rows, ac->n_joints = n;
+    ac->params_at = ((size_t)n * sizeof(int32_t) + 15) / 16 * 16;
+    std::vector<unsigned char> host(ac->params_at + (size_t)n * sizeof(jxs_act::Params<T>), 0);
+    int32_t* codes = reinterpret_cast<int32_t*>(host.data());
+    jxs_act::Params<T>* pr = reinterpret_cast<jxs_act::Params<T>*>(host.data() + ac->params_at);
+    for (int j = 0; j < n; ++j) {
+      codes[j] = jxs_act::pack_joint(joints[2 * j], joints[2 * j + 1]);
+      ac->reads_actions = ac->reads_actions || joints[2 * j + 1] >= 0;
+      for (int k = 0; k < jxs_act::kParams; ++k) pr[j].v[k] = static_cast<T>(params[jxs_act::kParams * j + k]);
+    }
+    JXS_HIP(hipMalloc(&ac->table, host.size()));
+    const hipError_t e = hipMemcpy(ac->table, host.data(), host.size(), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+      (void)hipFree(ac->table);
+      return hip_fail(e, "uploading the action table");
+    }
+    *out = ac.release();
+    return JXS_OK;
+  });
+}
+int jxs_action_destroy(jxs_action* action) {
+  if (action == nullptr) return JXS_OK;
+  (void)hipFree(action->table);  // (hipFree waits for the launches that may still read the table)
+  delete action;
+  return JXS_OK;
+}
+
+int jxs_env_act(jxs_model* model, const jxs_action* action, const void* state, const void* actions, int act_dtype, int64_t act_ld,
+                const void* feed_forward, void* out_tau, int N, void* stream) {
+  if (model == nullptr || action == nullptr || state == nullptr || out_tau == nullptr) return fail(JXS_EINVAL, "jxs_env_act: null argument");
+  if (N <= 0) return fail(JXS_EINVAL, "jxs_env_act: N must be positive");
+  if (act_dtype != JXS_F32 && act_dtype != JXS_F64) return fail(JXS_EINVAL, "jxs_env_act: unknown act_dtype");
+  if (act_dtype != JXS_F32 && act_dtype != model->dtype) return fail(JXS_EINVAL, "jxs_env_act: act_dtype must be JXS_F32 or the model's dtype");
+  const jxs_action& ac = *action;
+  if (act_ld < ac.A) return fail(JXS_EINVAL, "jxs_env_act: act_ld = " + std::to_string(act_ld) + " below A = " + std::to_string(ac.A));
+  if (ac.reads_actions && actions == nullptr) return fail(JXS_EINVAL, "jxs_env_act: the table reads action columns, and actions is null");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int rc = with_typed(model, [&](auto* mt) {
+    using T = typename std::remove_pointer_t<decltype(mt)>::value_type;
+    const auto& P = mt->pk.P;
+    if (ac.dtype != model->dtype || ac.n_rows != P.n_rows || ac.n_joints != P.n)
+      return fail(JXS_EINVAL, "jxs_env_act: the action table was created for another state layout or dtype");
+    const int tile = 64 / mt->pk.G;
+    int tile_shift = 0;
+    while ((1 << tile_shift) < tile) ++tile_shift;
+    if (tile <= 0 || (1 << tile_shift) != tile || tile > 64) return fail(JXS_EINVAL, "jxs_env_act: the model's tile does not divide the wave");
+    if (jxs_env::tile_words(P.n_rows, tile) >= (1LL << 30)) return fail(JXS_EINVAL, "jxs_env_act: rows * tile must be below 2^30");
+    const size_t ab = act_dtype == JXS_F64 ? 8 : 4;
+    const void* act = ac.reads_actions ? actions : nullptr;  // (a tensor the table does not read is not looked at)
+    if ((uintptr_t)state % sizeof(T) != 0 || (uintptr_t)out_tau % sizeof(T) != 0 || (uintptr_t)feed_forward % sizeof(T) != 0 || (uintptr_t)act % ab != 0)
+      return fail(JXS_EINVAL, "jxs_env_act: state, actions, feed_forward and out_tau must be aligned to their element type");
+    // The widest access that the span of the n joint rows of a tile, the tile span of the state, the places of the q and qd
+    // rows in it and the three block addresses allow.  (The humanoid in fp32: 23 x 2 x 4 = 184 bytes, rows at 56 and 288: 8.)
+    const int wb = (int)sizeof(T), n = P.n;
+    const unsigned long long q_at = (unsigned long long)jxs_act::row_q(n) * tile * wb, qd_at = (unsigned long long)jxs_act::row_qd(n) * tile * wb;
+    const int access = std::min(jxs_env::access_bytes((unsigned long long)(uintptr_t)out_tau | (unsigned long long)(uintptr_t)feed_forward, n, tile, wb),
+                                jxs_env::access_bytes((unsigned long long)(uintptr_t)state | q_at | qd_at, P.n_rows, tile, wb));
+    // Environments per wave, E = 2^env_shift with T <= E <= max(T, 32), by the rule of jxs_env_observe: as many as still leave
+    // the chip 8192 waves.  Measured on the humanoid (profiles/env_act.txt): at N = 65 536 a wave of 4, 8 or 16 environments
+    // takes 7.2 .. 7.4 us, one of 2 or 32 about 11 us; at N = 1024 everything up to 8 is one launch interval (3.6 us).
+    int knobs, duo_blocks;
+    debug_knobs(knobs, duo_blocks);  // (reads the environment on the first call of the process)
+    (void)knobs, (void)duo_blocks;
+    const int want = g_act_envs_per_wave.load(std::memory_order_relaxed);
+    int env_shift = tile_shift;
+    const int max_shift = std::max(tile_shift, 5);
+    if (want > 0) {
+      while (env_shift < max_shift && (1 << env_shift) < want) ++env_shift;
+    } else {
+      while (env_shift < max_shift && ((long long)N >> (env_shift + 1)) >= 8192) ++env_shift;
+    }
+    const long long waves = ((long long)N + (1LL << env_shift) - 1) >> env_shift;
+    const dim3 grid((unsigned)((waves + 3) / 4));
+    if (act_dtype == model->dtype)
+      launch_env_act<T, T>(access, grid, s, state, act, (long long)act_ld, ac, feed_forward, out_tau, N, tile_shift, env_shift);
+    else
+      launch_env_act<T, float>(access, grid, s, state, act, (long long)act_ld, ac, feed_forward, out_tau, N, tile_shift, env_shift);
+    return (int)JXS_OK;
+  });
+  if (rc != JXS_OK) return rc;
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(e, "jxs_env_act");
   return JXS_OK;
 }
 

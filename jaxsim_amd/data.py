@@ -575,6 +575,73 @@ class JaxSimModelData:
         )
         return out
 
+    def _action_tensor(self, spec: "ActionSpec", actions):
+        """``(object to keep alive until the launch is enqueued, device pointer or None, leading dimension, dtype)`` of the
+        ``actions`` argument of ``act``; a host array is uploaded on the current stream."""
+        N, A, dt = self._state.cols, spec.width, self.dtype
+        if actions is None:
+            if spec.reads_actions:
+                raise ValueError("actions is None, and the spec names action columns")
+            return None, None, A, np.dtype(np.float32)
+        if isinstance(actions, runtime.DeviceMatrix):
+            if actions.shape != (N, A) or actions.dtype not in (np.dtype(np.float32), dt):
+                raise ValueError(f"actions is {actions.shape} {actions.dtype}: expected ({N}, {A}) float32 or {dt}")
+            return actions, actions.ptr, A, actions.dtype
+        if hasattr(actions, "__cuda_array_interface__"):
+            ptr, ld, adt = runtime.foreign_matrix(actions, N, A, tuple({"<f4", dt.str}), writable=False)
+            return actions, ptr, ld, adt
+        a = np.asarray(actions)
+        if a.dtype not in (np.dtype(np.float32), dt):
+            a = a.astype(dt)
+        if a.shape == (A,) and not self._batched:
+            a = a.reshape(1, A)
+        if a.shape != (N, A):
+            raise ValueError(f"actions of shape {a.shape}: expected ({N}, {A})")
+        m = runtime.DeviceMatrix.from_host(a)
+        return m, m.ptr, A, m.dtype
+
+    def act(self, spec: "ActionSpec", actions, *, feed_forward=None, out=None) -> runtime.DeviceArray:
+        """The joint torques of a policy's action, a tiled ``[n][batch_size]`` ``runtime.DeviceArray``, computed by one kernel
+        (``jxs_env_act``) on the current stream from the action tensor and this object's joint positions and velocities -- the
+        controller that the reference's user carries through a ``jax.lax.scan`` of ``step`` under ``vmap``: no download, no
+        synchronisation.  The result goes straight into ``step(joint_force_references=...)``.
+
+        ``actions``: a ``runtime.DeviceMatrix`` ``(batch_size, spec.width)``; any object with a 2-D
+        ``__cuda_array_interface__`` of that shape, typestr float32 or this object's dtype and strides ``None`` or
+        ``(ld * itemsize, itemsize)`` (read in place, zero copy); a host array of that shape (uploaded); ``None`` when the spec
+        names no column.  ``feed_forward``: a ``DeviceArray`` ``[n][batch_size]`` of this object's dtype and tile added before
+        the torque limit (what ``gravity_compensation_torques`` returns).  ``out``: such an array to write into.
+        ``ValueError`` before any launch for a spec of another layout or dtype, a wrong ``actions`` shape or dtype, a
+        mis-shaped ``feed_forward`` or ``out``."""
+        from .api.model import _device_model_fast
+
+        if not isinstance(spec, ActionSpec):
+            raise ValueError(f"spec must be an ActionSpec, not {type(spec).__name__}")
+        st = self._state
+        if spec.layout != StateLayout.of(self._model_ref) or spec.layout.n_rows != st.rows:
+            raise ValueError(f"spec was built for another model layout ({spec.layout} != {StateLayout.of(self._model_ref)})")
+        if spec.dtype != self.dtype:
+            raise ValueError(f"spec was built for dtype {spec.dtype}, not {self.dtype}")
+        N, n = st.cols, spec.layout.n_joints
+        for name, blk in (("feed_forward", feed_forward), ("out", out)):
+            if blk is None:
+                continue
+            if not isinstance(blk, runtime.DeviceArray):
+                raise ValueError(f"{name} must be a runtime.DeviceArray, not {type(blk).__name__}")
+            if blk.shape != (n, N) or blk.dtype != st.dtype or blk.tile != st.tile:
+                raise ValueError(f"{name} is {blk.shape} {blk.dtype} tile {blk.tile}: expected ({n}, {N}) {st.dtype} tile {st.tile}")
+        keep, aptr, ld, adt = self._action_tensor(spec, actions)
+        if out is None:
+            out = runtime.DeviceArray(n, N, st.dtype, tile=st.tile)
+        dm = _device_model_fast(self._model_ref, self.dtype)
+        _lib.check(
+            _lib.load().jxs_env_act(dm.handle, spec._table(dm), st.ptr, aptr, _lib.dtype_code(adt), ld,
+                                    None if feed_forward is None else feed_forward.ptr, out.ptr, N, runtime._sp()),
+            "jxs_env_act",
+        )  # fmt: skip
+        del keep
+        return out
+
 
 def random_model_data(
     model,
@@ -900,5 +967,185 @@ class ObservationSpec:
             self._handle = None
             try:
                 _lib.load().jxs_observation_destroy(h)
+            except Exception:
+                pass
+
+
+# modes of an action-table entry (JXS_ACT_* of include/jaxsim_amd.h) and the order of its eight parameters
+ACT_OFF, ACT_TORQUE, ACT_POSITION, ACT_VELOCITY = range(4)
+ACT_MODES = {"off": ACT_OFF, "torque": ACT_TORQUE, "position": ACT_POSITION, "velocity": ACT_VELOCITY}
+ACT_PARAMS = ("scale", "offset", "kp", "kd", "action_clip", "target_lo", "target_hi", "torque_limit")
+ACT_MAX_WIDTH = 4096
+
+
+class ActionSpec:
+    """How ``JaxSimModelData.act`` turns a policy's action tensor into joint torques for one model: one entry per joint of
+    the model, ``(mode, column)`` and the eight parameters ``ACT_PARAMS`` (the table of ``jxs_action_create``).  Built once on
+    the host -- no device is needed --, uploaded at the first ``act``, used for every sub-step of a loop.
+
+    ``joints`` ``[n, 2]`` int32, ``params`` ``[n, 8]`` float64, ``width``: the columns of the action tensor,
+    ``joint_names``: the joints the policy drives, in column order, ``columns``: joint name -> column."""
+
+    def __init__(self, layout: StateLayout, dtype, joints, params, width: int, joint_names):
+        self.layout = layout
+        self.dtype = np.dtype(dtype)
+        self.joints = np.ascontiguousarray(joints, dtype=np.int32).reshape(-1, 2)
+        self.params = np.ascontiguousarray(params, dtype=np.float64).reshape(-1, 8)
+        self.width = int(width)
+        self.joint_names = tuple(joint_names)
+        self.columns = {nm: c for c, nm in enumerate(self.joint_names)}
+        self._handles = {}
+
+    @property
+    def reads_actions(self) -> bool:
+        return bool((self.joints[:, 1] >= 0).any())
+
+    @staticmethod
+    def build(model, *, dtype=np.float32, joints=None, mode="position", kp=0.0, kd=0.0, scale=1.0, offset=0.0, action_clip=np.inf,
+              clip_to_position_limits=False, target_limits=None, torque_limit=np.inf, hold=None, hold_kp=None, hold_kd=None,
+              width=None) -> "ActionSpec":  # fmt: skip
+        """``joints`` names and orders the action columns (column ``c`` drives ``joints[c]``; the default is every joint, in
+        model order).  Per named joint, with ``a`` its action word:
+
+            u   = clamp(a, -action_clip, action_clip) * scale + offset
+            tau = "torque"    u
+                  "position"  kp * (clamp(u, target_lo, target_hi) - q) - kd * qdot
+                  "velocity"  kd * (u - qdot)
+                  "off"       0
+            tau = clamp(tau [+ feed_forward], -torque_limit, torque_limit)
+
+        ``mode`` and every numeric option is a scalar, one value per named joint, or a ``{joint name: value}`` dict (joints it
+        leaves out keep the default).  ``target_limits=(lo, hi)``, each in one of these forms; ``clip_to_position_limits=True``
+        takes the model's position limits instead.  ``hold={name: q}`` gives joints the policy does not drive a ``"position"``
+        entry without a column that holds ``q`` with ``hold_kp`` / ``hold_kd`` (scalars or dicts over the held joints; the
+        default is a scalar ``kp`` / ``kd``); a scalar or dict ``torque_limit`` applies to them too.  Joints neither named nor
+        held are ``"off"``.  ``width``: the action tensor's column count, ``len(joints)`` by default.
+
+        ``ValueError`` for an unknown joint or mode, a joint named twice or both named and held, a value that is not finite
+        in ``dtype``, negative or NaN limits, ``lo > hi``, a width below ``len(joints)`` or above 4096, a model without joints."""
+        lay = StateLayout.of(model)
+        dt = np.dtype(dtype)
+        _lib.dtype_code(dt)
+        n = lay.n_joints
+        if n < 1:
+            raise ValueError("the model has no joints: there is nothing to actuate")
+        names = list(model.joint_names())
+        known = {nm: i for i, nm in enumerate(names)}
+        named = list(names if joints is None else joints)
+        if isinstance(joints, (str, bytes)):
+            raise ValueError("joints must be a sequence of joint names, not one string")
+        missing = [j for j in named if j not in known]
+        if missing:
+            raise ValueError(f"unknown joints {missing}")
+        if len(set(named)) != len(named):
+            raise ValueError("a joint is named twice")
+        hold = dict(hold or {})
+        missing = [j for j in hold if j not in known]
+        if missing:
+            raise ValueError(f"hold: unknown joints {missing}")
+        both = [j for j in hold if j in named]
+        if both:
+            raise ValueError(f"joints {both} are both named and held")
+        k = len(named)
+        A = k if width is None else int(width)
+        if A < k or A > ACT_MAX_WIDTH:
+            raise ValueError(f"width {A}: expected {k} .. {ACT_MAX_WIDTH}")
+
+        def per_joint(what, value, default, over, convert=float):
+            """One value per joint of ``over`` from a scalar, a sequence or a {name: value} dict."""
+            if isinstance(value, dict):
+                unknown = [j for j in value if j not in over]
+                if unknown:
+                    raise ValueError(f"{what}: joints {unknown} are not among {list(over)}")
+                return [convert(value.get(j, default)) for j in over]
+            if isinstance(value, (str, bytes)) or np.ndim(value) == 0:
+                return [convert(value)] * len(over)
+            vals = list(value)
+            if len(vals) != len(over):
+                raise ValueError(f"{what}: {len(vals)} values for {len(over)} joints")
+            return [convert(v) for v in vals]
+
+        def mode_code(m):
+            if isinstance(m, str) and m in ACT_MODES:
+                return ACT_MODES[m]
+            raise ValueError(f"unknown mode {m!r}: expected one of {sorted(ACT_MODES)}")
+
+        if clip_to_position_limits and target_limits is not None:
+            raise ValueError("give either clip_to_position_limits or target_limits")
+        if target_limits is not None:
+            if not isinstance(target_limits, (tuple, list)) or len(target_limits) != 2:
+                raise ValueError("target_limits must be a pair (lo, hi)")
+            t_lo, t_hi = target_limits
+        elif clip_to_position_limits:
+            kdp = model.kin_dyn_parameters
+            lo_all, hi_all = np.asarray(kdp.position_limits_min, dtype=float), np.asarray(kdp.position_limits_max, dtype=float)
+            t_lo, t_hi = [lo_all[known[j]] for j in named], [hi_all[known[j]] for j in named]
+        else:
+            t_lo, t_hi = -np.inf, np.inf
+        cols = {
+            "mode": per_joint("mode", mode, "position", named, mode_code),
+            "scale": per_joint("scale", scale, 1.0, named), "offset": per_joint("offset", offset, 0.0, named),
+            "kp": per_joint("kp", kp, 0.0, named), "kd": per_joint("kd", kd, 0.0, named),
+            "action_clip": per_joint("action_clip", action_clip, np.inf, named),
+            "target_lo": per_joint("target_limits[0]", t_lo, -np.inf, named), "target_hi": per_joint("target_limits[1]", t_hi, np.inf, named),
+        }  # fmt: skip
+        held = list(hold)
+        everyone = named + held
+        if isinstance(torque_limit, dict) or np.ndim(torque_limit) == 0:
+            limits = per_joint("torque_limit", torque_limit, np.inf, everyone)
+        else:
+            limits = per_joint("torque_limit", torque_limit, np.inf, named) + [np.inf] * len(held)
+        h_kp = h_kd = []
+        if held:  # (without held joints the hold gains are not looked at: kp / kd may then have any of their forms)
+            for what, own, general in (("hold_kp", hold_kp, kp), ("hold_kd", hold_kd, kd)):
+                if own is None and (isinstance(general, dict) or np.ndim(general) != 0):
+                    raise ValueError(f"{what} is needed: {what[5:]} is not a scalar")
+            h_kp = per_joint("hold_kp", kp if hold_kp is None else hold_kp, 0.0, held)
+            h_kd = per_joint("hold_kd", kd if hold_kd is None else hold_kd, 0.0, held)
+        table = np.full((n, 2), (ACT_OFF, -1), dtype=np.int32)
+        params = np.tile(np.array([1.0, 0.0, 0.0, 0.0, np.inf, -np.inf, np.inf, np.inf]), (n, 1))
+        for c, j in enumerate(named):
+            table[known[j]] = (cols["mode"][c], c)
+            params[known[j]] = [cols[p][c] for p in ACT_PARAMS[:-1]] + [limits[c]]
+        for i, j in enumerate(held):
+            table[known[j]] = (ACT_POSITION, -1)
+            params[known[j]] = [1.0, float(hold[j]), h_kp[i], h_kd[i], np.inf, -np.inf, np.inf, limits[k + i]]
+
+        def finite(v):
+            with np.errstate(over="ignore"):
+                return bool(np.isfinite(v) and np.isfinite(np.float64(v).astype(dt)))
+
+        for i in range(n):
+            p = dict(zip(ACT_PARAMS, params[i]))
+            for what in ("scale", "offset", "kp", "kd"):
+                if not finite(p[what]):
+                    raise ValueError(f"joint {names[i]!r}: {what} = {p[what]} is not finite in {dt.name}")
+            for what in ("action_clip", "torque_limit"):
+                if not (p[what] >= 0 and (np.isposinf(p[what]) or finite(p[what]))):
+                    raise ValueError(f"joint {names[i]!r}: {what} = {p[what]}: expected a value >= 0 that is finite in {dt.name}, or +inf")
+            lo, hi = p["target_lo"], p["target_hi"]
+            if not (lo <= hi and all(np.isinf(v) or finite(v) for v in (lo, hi))):
+                raise ValueError(f"joint {names[i]!r}: target limits ({lo}, {hi}): expected lo <= hi, each infinite or finite in {dt.name}")
+        return ActionSpec(lay, dt, table, params, A, named)
+
+    def _table(self, dm) -> C.c_void_p:
+        """The device table (``jxs_action``), uploaded at the first use and kept per device model: one small allocation and
+        a blocking copy."""
+        rec = self._handles.get(id(dm))
+        if rec is None:
+            h = C.c_void_p()
+            _lib.check(
+                _lib.load().jxs_action_create(dm.handle, self.width, self.joints.ctypes.data_as(C.POINTER(C.c_int32)),
+                                              self.params.ctypes.data_as(C.POINTER(C.c_double)), C.byref(h)),
+                "jxs_action_create",
+            )  # fmt: skip
+            rec = self._handles[id(dm)] = (dm, h)  # (the device model is kept alive with the table made from it)
+        return rec[1]
+
+    def __del__(self):
+        handles, self._handles = getattr(self, "_handles", {}), {}
+        for _dm, h in handles.values():
+            try:
+                _lib.load().jxs_action_destroy(h)
             except Exception:
                 pass

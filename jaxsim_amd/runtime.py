@@ -430,12 +430,23 @@ class DeviceMatrix:
     def to_host(self) -> np.ndarray:
         return self._buf.to_host_raw().reshape(self.n, self.width)
 
+    @staticmethod
+    def from_host(a: np.ndarray) -> "DeviceMatrix":
+        """Upload a host ``(n, width)`` array of float32 / float64 on the current stream."""
+        a = np.ascontiguousarray(a)
+        if a.ndim != 2:
+            raise ValueError("expected an (n, width) array")
+        out = DeviceMatrix(a.shape[0], a.shape[1], a.dtype)
+        _lib.check(_lib.load().jxs_memcpy_h2d(C.c_void_p(out.ptr), a.ctypes.data_as(C.c_void_p), a.nbytes, _sp()), "jxs_memcpy_h2d")
+        return out
 
-def foreign_matrix(obj, n: int, width: int, typestrs: tuple) -> tuple[int, int, np.dtype]:
+
+def foreign_matrix(obj, n: int, width: int, typestrs: tuple, *, writable: bool = True) -> tuple[int, int, np.dtype]:
     """``(device pointer, leading dimension in elements, dtype)`` of an object that speaks ``__cuda_array_interface__``,
     used with ZERO copy as an environment-major ``(n, width)`` matrix: 2-D, of that shape, of one of ``typestrs``, its
-    strides ``None`` or ``(ld * itemsize, itemsize)`` with ``ld >= width``; ``ValueError`` otherwise.  The caller keeps
-    ``obj`` alive and orders the stream that reads it behind the current one."""
+    strides ``None`` or ``(ld * itemsize, itemsize)`` with ``ld >= width``; ``ValueError`` otherwise.  A read-only array
+    is refused unless ``writable=False`` (the matrix is only read).  The caller keeps ``obj`` alive and orders the stream
+    that reads it behind the current one."""
     cai = obj.__cuda_array_interface__
     shape = tuple(cai["shape"])
     if shape != (n, width):
@@ -453,7 +464,7 @@ def foreign_matrix(obj, n: int, width: int, typestrs: tuple) -> tuple[int, int, 
     ptr = cai["data"][0]
     if not ptr:
         raise ValueError("device array with a null pointer")
-    if cai["data"][1]:
+    if cai["data"][1] and writable:
         raise ValueError("device array is read-only")
     return int(ptr), int(ld), dt
 
