@@ -68,11 +68,13 @@ void load_knobs() {
   g_duo_max_blocks.store(b == nullptr ? 0 : std::atoi(b));
   g_knobs.store(k);
 }
-void debug_knobs(int& knobs, int& duo_max_blocks) {
+// one knob, after the read of the environment on the first call of the process
+int knob(const std::atomic<int>& k) {
   static std::once_flag once;
   std::call_once(once, load_knobs);
-  knobs = g_knobs.load(std::memory_order_relaxed), duo_max_blocks = g_duo_max_blocks.load(std::memory_order_relaxed);
+  return k.load(std::memory_order_relaxed);
 }
+void debug_knobs(int& knobs, int& duo_max_blocks) { knobs = knob(g_knobs), duo_max_blocks = knob(g_duo_max_blocks); }
 }  // namespace
 
 namespace {
@@ -842,30 +844,73 @@ __global__ void __launch_bounds__(256) jxs_env_act_kernel(const T* __restrict__ 
 }
 
 namespace {
-template <int A, int WB>
-void launch_env_select(const uint8_t* mask, const void* a, const void* b, void* out, int rows, int N, int tile, hipStream_t s) {
-  const long long tiles = jxs_env::n_tiles(N, tile);
-  hipLaunchKernelGGL((jxs_env_select_kernel<A, WB>), dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, s, mask, (const unsigned char*)a,
-                     (const unsigned char*)b, (unsigned char*)out, rows, N, tile, tiles);
+// ---- the host side of the per-environment operations (jxs_env_*, jxs_observation_*, jxs_action_*): what their entry
+// points share.  Every refusal comes before the launch and names its entry point (`who`).
+
+int refuse(const char* who, const std::string& what) { return fail(JXS_EINVAL, std::string(who) + ": " + what); }
+
+bool repr_ok(int r) { return r == JXS_REPR_INERTIAL || r == JXS_REPR_BODY || r == JXS_REPR_MIXED; }
+
+// The env kernels' view of a model: a tile of T = 64 / G = 2^tile_shift environments, whole tiles per wave, and the words
+// of a tile of `rows` rows (the state's, or the tallest block the launch reads) counted in 32 bits with room to spare.
+struct EnvTile {
+  int tile = 0, tile_shift = 0;
+};
+int env_tile(const char* who, int G, int rows, EnvTile& t) {
+  t.tile = G > 0 ? 64 / G : 0, t.tile_shift = 0;
+  while ((1 << t.tile_shift) < t.tile) ++t.tile_shift;
+  if (t.tile <= 0 || (1 << t.tile_shift) != t.tile || t.tile > 64) return refuse(who, "the model's tile does not divide the wave");
+  if (jxs_env::tile_words(rows, t.tile) >= (1LL << 30)) return refuse(who, "rows * tile must be below 2^30");
+  return JXS_OK;
 }
 
-template <typename T, typename AT>
-void launch_env_act(int access, dim3 grid, hipStream_t s, const void* state, const void* actions, long long act_ld, const jxs_action& ac,
-                    const void* ff, void* out, int N, int tile_shift, int env_shift) {
-  const unsigned char* tb = static_cast<const unsigned char*>(ac.table);
-  const int32_t* codes = reinterpret_cast<const int32_t*>(tb);
-  const jxs_act::Params<T>* params = reinterpret_cast<const jxs_act::Params<T>*>(tb + ac.params_at);
-#define JXS_ACT_LAUNCH(AB)                                                                                                                    \
-  hipLaunchKernelGGL((jxs_env_act_kernel<T, AT, AB>), grid, dim3(256), 0, s, static_cast<const T*>(state), static_cast<const AT*>(actions), act_ld, \
-                     codes, params, static_cast<const T*>(ff), static_cast<T*>(out), ac.n_joints, ac.n_rows, N, tile_shift, env_shift)
-  if (access == 16) {
-    JXS_ACT_LAUNCH(16);
-  } else if (access == 8) {
-    JXS_ACT_LAUNCH(8);
-  } else if constexpr (sizeof(T) == 4) {
-    JXS_ACT_LAUNCH(4);
-  }
-#undef JXS_ACT_LAUNCH
+// f(std::integral_constant<int, A>) for the access width A = `access` out of {16, 8, 4} bytes (jxs_env::access_bytes, never
+// below the word): the kernels take it at compile time, and words of WB = 8 bytes have no 4-byte variant.
+template <int WB, typename F>
+void with_access(int access, F&& f) {
+  if (access == 16) f(std::integral_constant<int, 16>{});
+  else if (access == 8) f(std::integral_constant<int, 8>{});
+  else if constexpr (WB == 4) f(std::integral_constant<int, 4>{});
+}
+// f(T{}) or f(float{}): the element type of the tensor a policy shares with the library, the model's own or float32
+template <typename T, typename F>
+void with_io_type(bool models_own, F&& f) {
+  if (models_own) f(T{});
+  else f(float{});
+}
+
+// the env kernels run four waves per workgroup, which share nothing
+constexpr int kEnvBlock = 256;
+dim3 env_grid(long long waves) { return dim3((unsigned)((waves + 3) / 4)); }
+long long env_waves(int N, int env_shift) { return ((long long)N + (1LL << env_shift) - 1) >> env_shift; }
+
+// after the launch: what the runtime says about it
+int launched(const char* who) {
+  const hipError_t e = hipGetLastError();
+  return e != hipSuccess ? hip_fail(e, who) : (int)JXS_OK;
+}
+
+// was this table (jxs_observation, jxs_action) created for the state layout and dtype of this model?
+template <typename Table, typename KP>
+bool table_fits(const Table& t, int dtype, const KP& P) {
+  return t.dtype == dtype && t.n_rows == P.n_rows && t.n_joints == P.n;
+}
+
+// A host table on the device (blocking; the tables are a few KB), null and the error set if that fails; and the end of a
+// table object.  hipFree waits for the launches that may still read the table.
+void* upload_table(const std::vector<unsigned char>& host, const char* what) {
+  void* d = nullptr;
+  hipError_t e = hipMalloc(&d, host.size());
+  if (e == hipSuccess && (e = hipMemcpy(d, host.data(), host.size(), hipMemcpyHostToDevice)) != hipSuccess) (void)hipFree(d);
+  if (e == hipSuccess) return d;
+  hip_fail(e, what);
+  return nullptr;
+}
+template <typename Table>
+int destroy_table(Table* t) {
+  if (t != nullptr) (void)hipFree(t->table);
+  delete t;
+  return JXS_OK;
 }
 
 template <typename T>
@@ -1116,18 +1161,17 @@ int jxs_env_select(const uint8_t* mask, const void* a, const void* b, void* out,
   if (addr % wb != 0) return fail(JXS_EINVAL, "a, b and out must be aligned to their element type");
   if (jxs_env::tile_words(rows, tile) >= (1LL << 30)) return fail(JXS_EINVAL, "rows * tile must be below 2^30");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const int access = jxs_env::access_bytes(addr, rows, tile, wb);
-  if (wb == 4) {
-    if (access == 16) launch_env_select<16, 4>(mask, a, b, out, rows, N, tile, s);
-    else if (access == 8) launch_env_select<8, 4>(mask, a, b, out, rows, N, tile, s);
-    else launch_env_select<4, 4>(mask, a, b, out, rows, N, tile, s);
-  } else {
-    if (access == 16) launch_env_select<16, 8>(mask, a, b, out, rows, N, tile, s);
-    else launch_env_select<8, 8>(mask, a, b, out, rows, N, tile, s);
-  }
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail(e, "jxs_env_select");
-  return JXS_OK;
+  const long long tiles = jxs_env::n_tiles(N, tile);
+  auto launch = [&](auto word) {  // (the kernel moves words as bytes: it takes their size, not their type)
+    constexpr int WB = decltype(word)::value;
+    with_access<WB>(jxs_env::access_bytes(addr, rows, tile, WB), [&](auto ab) {
+      hipLaunchKernelGGL((jxs_env_select_kernel<decltype(ab)::value, WB>), env_grid(tiles), dim3(kEnvBlock), 0, s, mask, (const unsigned char*)a,
+                         (const unsigned char*)b, (unsigned char*)out, rows, N, tile, tiles);
+    });
+  };
+  if (wb == 4) launch(std::integral_constant<int, 4>{});
+  else launch(std::integral_constant<int, 8>{});
+  return launched("jxs_env_select");
 }
 
 int jxs_env_copy(const void* src, int src_N, int src_tile, const int32_t* src_idx, void* dst, int dst_N, int dst_tile,
@@ -1141,56 +1185,45 @@ int jxs_env_copy(const void* src, int src_N, int src_tile, const int32_t* src_id
   const long long blocks = (total + threads - 1) / threads;
   if (blocks > 0x7fffffffLL) return fail(JXS_EINVAL, "K * rows is too large for one launch");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (dtype == JXS_F64)
-    hipLaunchKernelGGL(jxs_env_copy_kernel<uint64_t>, dim3((unsigned)blocks), dim3(threads), 0, s, (const uint64_t*)src, src_N, src_tile, src_idx,
-                       (uint64_t*)dst, dst_N, dst_tile, dst_idx, rows, total);
-  else
-    hipLaunchKernelGGL(jxs_env_copy_kernel<uint32_t>, dim3((unsigned)blocks), dim3(threads), 0, s, (const uint32_t*)src, src_N, src_tile, src_idx,
-                       (uint32_t*)dst, dst_N, dst_tile, dst_idx, rows, total);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail(e, "jxs_env_copy");
-  return JXS_OK;
+  with_dtype(dtype, [&](auto zero) {
+    using W = std::conditional_t<sizeof(zero) == 8, uint64_t, uint32_t>;  // (words are moved as bits)
+    hipLaunchKernelGGL(jxs_env_copy_kernel<W>, dim3((unsigned)blocks), dim3(threads), 0, s, (const W*)src, src_N, src_tile, src_idx, (W*)dst,
+                       dst_N, dst_tile, dst_idx, rows, total);
+  });
+  return launched("jxs_env_copy");
 }
 
 int jxs_env_flags(jxs_model* model, const void* state, int N, uint8_t* out_flags, void* stream) {
   if (model == nullptr || state == nullptr || out_flags == nullptr) return fail(JXS_EINVAL, "null argument");
   if (N <= 0) return fail(JXS_EINVAL, "N must be positive");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const int rc = with_typed(model, [&](auto* mt) {
+  return with_typed(model, [&](auto* mt) {
     using T = typename std::remove_pointer_t<decltype(mt)>::value_type;
     const auto& P = mt->pk.P;
-    const int tile = 64 / mt->pk.G;
-    if (tile <= 0 || 64 % tile != 0) return fail(JXS_EINVAL, "jxs_env_flags: the model's tile does not divide the wave");
-    if (jxs_env::tile_words(P.n_rows, tile) >= (1LL << 30)) return fail(JXS_EINVAL, "jxs_env_flags: rows * tile must be below 2^30");
-    const long long tiles = jxs_env::n_tiles(N, tile);
-    hipLaunchKernelGGL(jxs_env_flags_kernel<T>, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, s, static_cast<const T*>(state), P.n_rows,
-                       P.row_quat, tile, N, tiles, out_flags);
-    return (int)JXS_OK;
+    EnvTile t;
+    if (const int rc = env_tile("jxs_env_flags", mt->pk.G, P.n_rows, t)) return rc;
+    const long long tiles = jxs_env::n_tiles(N, t.tile);
+    hipLaunchKernelGGL(jxs_env_flags_kernel<T>, env_grid(tiles), dim3(kEnvBlock), 0, s, static_cast<const T*>(state), P.n_rows, P.row_quat,
+                       t.tile, N, tiles, out_flags);
+    return launched("jxs_env_flags");
   });
-  if (rc != JXS_OK) return rc;
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail(e, "jxs_env_flags");
-  return JXS_OK;
 }
 
 int jxs_env_randomize(jxs_model* model, const uint8_t* mask, void* state, int N, const void* bounds, uint64_t seed, uint64_t draw,
                       int64_t first_env, int velocity_representation, void* stream) {
   if (model == nullptr || state == nullptr || bounds == nullptr) return fail(JXS_EINVAL, "null argument");
   if (N <= 0) return fail(JXS_EINVAL, "N must be positive");
-  if (!jxs_rand::env_range_ok(first_env, N)) return fail(JXS_EINVAL, "jxs_env_randomize: first_env must be >= 0 and first_env + N <= 2^32");
-  if (velocity_representation != JXS_REPR_INERTIAL && velocity_representation != JXS_REPR_BODY && velocity_representation != JXS_REPR_MIXED)
-    return fail(JXS_EINVAL, "jxs_env_randomize: unknown velocity representation");
+  const char* const who = "jxs_env_randomize";
+  if (!jxs_rand::env_range_ok(first_env, N)) return refuse(who, "first_env must be >= 0 and first_env + N <= 2^32");
+  if (!repr_ok(velocity_representation)) return refuse(who, "unknown velocity representation");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const int rc = with_typed(model, [&](auto* mt) {
+  return with_typed(model, [&](auto* mt) {
     using T = typename std::remove_pointer_t<decltype(mt)>::value_type;
     const auto& P = mt->pk.P;
-    const int tile = 64 / mt->pk.G;
-    int tile_shift = 0;
-    while ((1 << tile_shift) < tile) ++tile_shift;
-    if (tile <= 0 || (1 << tile_shift) != tile || tile > 64) return fail(JXS_EINVAL, "jxs_env_randomize: the model's tile does not divide the wave");
-    if (jxs_env::tile_words(P.n_rows, tile) >= (1LL << 30)) return fail(JXS_EINVAL, "jxs_env_randomize: rows * tile must be below 2^30");
-    if ((uintptr_t)state % sizeof(T) != 0 || (uintptr_t)bounds % sizeof(T) != 0)
-      return fail(JXS_EINVAL, "jxs_env_randomize: state and bounds must be aligned to their element type");
+    EnvTile t;
+    if (const int rc = env_tile(who, mt->pk.G, P.n_rows, t)) return rc;
+    const int tile = t.tile;
+    if ((uintptr_t)state % sizeof(T) != 0 || (uintptr_t)bounds % sizeof(T) != 0) return refuse(who, "state and bounds must be aligned to their element type");
     const jxs_rand::Shape shape{P.n, P.floating, velocity_representation};
     // LDS of a workgroup: four waves, each the variables and the derived values of the T environments of its tile.
     // The packer gives an environment G >= max(4, pow2ceil(n_links)) lanes (jxs_pack.h), so T = 64 / G <= 16 and
@@ -1199,24 +1232,15 @@ int jxs_env_randomize(jxs_model* model, const uint8_t* mask, void* state, int N,
     // many joints) fails here with a message instead of launching with more LDS than a workgroup may have -- the
     // remedy then is fewer waves per workgroup, not a larger limit.
     const size_t lds = 4 * (size_t)(jxs_rand::n_variables(P.n) + jxs_rand::kDerived) * tile * sizeof(T);
-    if (lds > 65536) return fail(JXS_EINVAL, "jxs_env_randomize: (12 + 2 n_joints + 10) * tile words per wave do not fit the LDS of a workgroup");
+    if (lds > 65536) return refuse(who, "(12 + 2 n_joints + 10) * tile words per wave do not fit the LDS of a workgroup");
     const long long tiles = jxs_env::n_tiles(N, tile);
-    const dim3 grid((unsigned)((tiles + 3) / 4)), block(256);
-    unsigned char* st = static_cast<unsigned char*>(state);
-    const T* bd = static_cast<const T*>(bounds);
-    const int access = jxs_env::access_bytes((unsigned long long)(uintptr_t)state, P.n_rows, tile, (int)sizeof(T));
-#define JXS_RANDOMIZE(A) \
-  hipLaunchKernelGGL((jxs_env_randomize_kernel<T, A>), grid, block, lds, s, mask, st, P.n_rows, N, tile_shift, tiles, shape, bd, seed, draw, (long long)first_env)
-    if (access == 16) JXS_RANDOMIZE(16);
-    else if (access == 8) JXS_RANDOMIZE(8);
-    else if constexpr (sizeof(T) == 4) JXS_RANDOMIZE(4);
-#undef JXS_RANDOMIZE
-    return (int)JXS_OK;
+    with_access<sizeof(T)>(jxs_env::access_bytes((unsigned long long)(uintptr_t)state, P.n_rows, tile, (int)sizeof(T)), [&](auto ab) {
+      hipLaunchKernelGGL((jxs_env_randomize_kernel<T, decltype(ab)::value>), env_grid(tiles), dim3(kEnvBlock), lds, s, mask,
+                         static_cast<unsigned char*>(state), P.n_rows, N, t.tile_shift, tiles, shape, static_cast<const T*>(bounds), seed, draw,
+                         (long long)first_env);
+    });
+    return launched(who);
   });
-  if (rc != JXS_OK) return rc;
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail(e, "jxs_env_randomize");
-  return JXS_OK;
 }
 
 int jxs_observation_create(jxs_model* model, int D, const int32_t* slots, const double* offset, const double* scale,
@@ -1225,25 +1249,26 @@ int jxs_observation_create(jxs_model* model, int D, const int32_t* slots, const 
   *out = nullptr;
   if (model == nullptr) return fail(JXS_EINVAL, "null model");
   if (slots == nullptr) return fail(JXS_EINVAL, "null slots");
+  const char* const who = "jxs_observation_create";
   return with_typed(model, [&](auto* mt) -> int {
     using T = typename std::remove_pointer_t<decltype(mt)>::value_type;
     const auto& P = mt->pk.P;
     int bad = -1;
     const int err = jxs_obs::table_error(slots, D, P.n_rows, source_rows, &bad);
     if (err == jxs_obs::kBadWidth)
-      return fail(JXS_EINVAL, "jxs_observation_create: D = " + std::to_string(D) + " outside [1, " + std::to_string(JXS_OBS_MAX_WIDTH) + "]");
+      return refuse(who, "D = " + std::to_string(D) + " outside [1, " + std::to_string(JXS_OBS_MAX_WIDTH) + "]");
     if (err != jxs_obs::kOk) {
       const char* what = err == jxs_obs::kBadKind ? "unknown kind" : err == jxs_obs::kBadSource ? "source out of range or without rows" : "row or component out of range";
-      return fail(JXS_EINVAL, "jxs_observation_create: slot " + std::to_string(bad) + " {" + std::to_string(slots[3 * bad]) + ", " +
-                                  std::to_string(slots[3 * bad + 1]) + ", " + std::to_string(slots[3 * bad + 2]) + "}: " + what);
+      return refuse(who, "slot " + std::to_string(bad) + " {" + std::to_string(slots[3 * bad]) + ", " + std::to_string(slots[3 * bad + 1]) + ", " +
+                             std::to_string(slots[3 * bad + 2]) + "}: " + what);
     }
     auto ob = std::make_unique<jxs_observation>();
     ob->dtype = model->dtype, ob->D = D, ob->n_rows = P.n_rows, ob->n_joints = P.n;
     for (int s = 0; s < jxs_obs::kSources; ++s) {
       ob->source_rows[s] = source_rows != nullptr && source_rows[s] > 0 ? source_rows[s] : 0;
-      if (ob->source_rows[s] >= (1 << 26)) return fail(JXS_EINVAL, "jxs_observation_create: a source of 2^26 rows or more");
+      if (ob->source_rows[s] >= (1 << 26)) return refuse(who, "a source of 2^26 rows or more");
     }
-    if (P.n_rows >= (1 << 26)) return fail(JXS_EINVAL, "jxs_observation_create: a state of 2^26 rows or more");
+    if (P.n_rows >= (1 << 26)) return refuse(who, "a state of 2^26 rows or more");
     ob->offset_at = ((size_t)D * sizeof(int32_t) + 15) / 16 * 16;
     ob->scale_at = ob->offset_at + ((size_t)D * sizeof(T) + 15) / 16 * 16;
     std::vector<unsigned char> host(ob->scale_at + (size_t)D * sizeof(T), 0);
@@ -1254,123 +1279,87 @@ int jxs_observation_create(jxs_model* model, int D, const int32_t* slots, const 
       const jxs_obs::Slot s{slots[3 * d], slots[3 * d + 1], slots[3 * d + 2]};
       const double o = offset != nullptr ? offset[d] : 0.0, c = scale != nullptr ? scale[d] : 1.0;
       if (!jxs_obs::affine_ok(o, T(0)) || !jxs_obs::affine_ok(c, T(0)))
-        return fail(JXS_EINVAL, "jxs_observation_create: slot " + std::to_string(d) + ": offset or scale not finite in the model's dtype");
+        return refuse(who, "slot " + std::to_string(d) + ": offset or scale not finite in the model's dtype");
       codes[d] = jxs_obs::pack_slot(s), off[d] = static_cast<T>(o), sc[d] = static_cast<T>(c);
       if (s.kind == jxs_obs::kSourceRow) ob->sources_used |= 1u << s.source;
     }
     for (int r = 0; r < 3; ++r) ob->derived_used[r] = jxs_obs::derived_used(slots, D, r);
-    JXS_HIP(hipMalloc(&ob->table, host.size()));
-    const hipError_t e = hipMemcpy(ob->table, host.data(), host.size(), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-      (void)hipFree(ob->table);
-      return hip_fail(e, "uploading the observation table");
-    }
+    if ((ob->table = upload_table(host, "uploading the observation table")) == nullptr) return JXS_ENODEVICE;
     *out = ob.release();
     return JXS_OK;
   });
 }
-int jxs_observation_destroy(jxs_observation* observation) {
-  if (observation == nullptr) return JXS_OK;
-  (void)hipFree(observation->table);  // (hipFree waits for the launches that may still read the table)
-  delete observation;
-  return JXS_OK;
-}
+int jxs_observation_destroy(jxs_observation* observation) { return destroy_table(observation); }
 
 int jxs_env_observe(jxs_model* model, const jxs_observation* observation, const void* state, const void* const sources[4], int N,
                     int velocity_representation, void* out, int out_dtype, int64_t out_ld, void* stream) {
-  if (model == nullptr || observation == nullptr || state == nullptr || out == nullptr) return fail(JXS_EINVAL, "jxs_env_observe: null argument");
-  if (N <= 0) return fail(JXS_EINVAL, "jxs_env_observe: N must be positive");
-  if (velocity_representation != JXS_REPR_INERTIAL && velocity_representation != JXS_REPR_BODY && velocity_representation != JXS_REPR_MIXED)
-    return fail(JXS_EINVAL, "jxs_env_observe: unknown velocity representation");
-  if (out_dtype != JXS_F32 && out_dtype != model->dtype) return fail(JXS_EINVAL, "jxs_env_observe: out_dtype must be JXS_F32 or the model's dtype");
+  const char* const who = "jxs_env_observe";
+  if (model == nullptr || observation == nullptr || state == nullptr || out == nullptr) return refuse(who, "null argument");
+  if (N <= 0) return refuse(who, "N must be positive");
+  if (!repr_ok(velocity_representation)) return refuse(who, "unknown velocity representation");
+  if (out_dtype != JXS_F32 && out_dtype != model->dtype) return refuse(who, "out_dtype must be JXS_F32 or the model's dtype");
   const jxs_observation& ob = *observation;
-  if (out_ld < ob.D) return fail(JXS_EINVAL, "jxs_env_observe: out_ld = " + std::to_string(out_ld) + " below D = " + std::to_string(ob.D));
+  if (out_ld < ob.D) return refuse(who, "out_ld = " + std::to_string(out_ld) + " below D = " + std::to_string(ob.D));
   ObsSources src{};
   for (int s = 0; s < jxs_obs::kSources; ++s) {
     if (!((ob.sources_used >> s) & 1u)) continue;  // (a pointer the table does not use is not looked at)
-    if (sources == nullptr || sources[s] == nullptr) return fail(JXS_EINVAL, "jxs_env_observe: the table reads source " + std::to_string(s) + ", whose pointer is null");
+    if (sources == nullptr || sources[s] == nullptr) return refuse(who, "the table reads source " + std::to_string(s) + ", whose pointer is null");
     src.ptr[s] = sources[s], src.rows[s] = ob.source_rows[s];
   }
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const int rc = with_typed(model, [&](auto* mt) {
+  return with_typed(model, [&](auto* mt) {
     using T = typename std::remove_pointer_t<decltype(mt)>::value_type;
     const auto& P = mt->pk.P;
-    if (ob.dtype != model->dtype || ob.n_rows != P.n_rows || ob.n_joints != P.n)
-      return fail(JXS_EINVAL, "jxs_env_observe: the observation table was created for another state layout or dtype");
-    const int tile = 64 / mt->pk.G;
-    int tile_shift = 0;
-    while ((1 << tile_shift) < tile) ++tile_shift;
-    if (tile <= 0 || (1 << tile_shift) != tile || tile > 64) return fail(JXS_EINVAL, "jxs_env_observe: the model's tile does not divide the wave");
+    if (!table_fits(ob, model->dtype, P)) return refuse(who, "the observation table was created for another state layout or dtype");
     int max_rows = P.n_rows;
     for (int k = 0; k < jxs_obs::kSources; ++k) max_rows = std::max(max_rows, src.rows[k]);
-    if (jxs_env::tile_words(max_rows, tile) >= (1LL << 30)) return fail(JXS_EINVAL, "jxs_env_observe: rows * tile must be below 2^30");
+    EnvTile t;
+    if (const int rc = env_tile(who, mt->pk.G, max_rows, t)) return rc;
     const size_t ob_bytes = out_dtype == JXS_F64 ? 8 : 4;
     bool aligned = (uintptr_t)state % sizeof(T) == 0 && (uintptr_t)out % ob_bytes == 0;
     for (int k = 0; k < jxs_obs::kSources; ++k) aligned = aligned && (uintptr_t)src.ptr[k] % sizeof(T) == 0;
-    if (!aligned) return fail(JXS_EINVAL, "jxs_env_observe: state, sources and out must be aligned to their element type");
-    // Environments per wave, E = 2^env_shift with T <= E <= max(T, 32): as many as still leave the chip 8192 waves (256 CUs x
-    // 4 SIMDs x 8), so that the table read and the derived values' prologue are shared by more environments at large N,
-    // while a small batch is spread over as many waves as it has tiles.  Measured on the humanoid (profiles/env_observe.txt):
-    // at N = 65 536 the 60-wide observation is fastest with 8 environments per wave (about 18.5 / 13 / 10.7 / 11.8 / 14.7 us
-    // with 2 / 4 / 8 / 16 / 32), at N = 1024 with one tile per wave (32 environments per wave take twice as long).
-    int knobs, duo_blocks;
-    debug_knobs(knobs, duo_blocks);  // (reads the environment on the first call of the process)
-    (void)knobs, (void)duo_blocks;
-    const int want = g_observe_envs_per_wave.load(std::memory_order_relaxed);
-    int env_shift = tile_shift;
-    const int max_shift = std::max(tile_shift, 5);
-    if (want > 0) {
-      while (env_shift < max_shift && (1 << env_shift) < want) ++env_shift;
-    } else {
-      while (env_shift < max_shift && ((long long)N >> (env_shift + 1)) >= 8192) ++env_shift;
-    }
+    if (!aligned) return refuse(who, "state, sources and out must be aligned to their element type");
+    const int env_shift = jxs_env::env_shift_for(N, t.tile_shift, knob(g_observe_envs_per_wave));
     const unsigned used = ob.derived_used[velocity_representation];
     const size_t lds = used != 0 ? 4 * (size_t)(jxs_obs::kDerived << env_shift) * sizeof(T) : 0;  // (at most 4 * 22 * 64 * 8 = 45 KB)
-    const long long waves = ((long long)N + (1LL << env_shift) - 1) >> env_shift;
-    const dim3 grid((unsigned)((waves + 3) / 4)), block(256);
     const jxs_obs::Shape sh{P.n_rows, P.n, velocity_representation};
     const unsigned char* tb = static_cast<const unsigned char*>(ob.table);
     const int32_t* codes = reinterpret_cast<const int32_t*>(tb);
     const T* off = reinterpret_cast<const T*>(tb + ob.offset_at);
     const T* sc = reinterpret_cast<const T*>(tb + ob.scale_at);
-    if (out_dtype == model->dtype)
-      hipLaunchKernelGGL((jxs_env_observe_kernel<T, T>), grid, block, lds, s, static_cast<const T*>(state), src, codes, off, sc, ob.D, used, sh, N,
-                         tile_shift, env_shift, static_cast<T*>(out), (long long)out_ld);
-    else
-      hipLaunchKernelGGL((jxs_env_observe_kernel<T, float>), grid, block, lds, s, static_cast<const T*>(state), src, codes, off, sc, ob.D, used, sh, N,
-                         tile_shift, env_shift, static_cast<float*>(out), (long long)out_ld);
-    return (int)JXS_OK;
+    with_io_type<T>(out_dtype == model->dtype, [&](auto o) {
+      using O = decltype(o);
+      hipLaunchKernelGGL((jxs_env_observe_kernel<T, O>), env_grid(env_waves(N, env_shift)), dim3(kEnvBlock), lds, s, static_cast<const T*>(state),
+                         src, codes, off, sc, ob.D, used, sh, N, t.tile_shift, env_shift, static_cast<O*>(out), (long long)out_ld);
+    });
+    return launched(who);
   });
-  if (rc != JXS_OK) return rc;
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail(e, "jxs_env_observe");
-  return JXS_OK;
 }
 
 int jxs_action_create(jxs_model* model, int A, const int32_t* joints, const double* params, jxs_action** out) {
   if (out == nullptr) return fail(JXS_EINVAL, "null out");
   *out = nullptr;
   if (model == nullptr) return fail(JXS_EINVAL, "null model");
-  if (joints == nullptr || params == nullptr) return fail(JXS_EINVAL, "jxs_action_create: null joints or params");
+  const char* const who = "jxs_action_create";
+  if (joints == nullptr || params == nullptr) return refuse(who, "null joints or params");
   return with_typed(model, [&](auto* mt) -> int {
     using T = typename std::remove_pointer_t<decltype(mt)>::value_type;
     const auto& P = mt->pk.P;
     const int n = P.n;
-    if (n < 1) return fail(JXS_EINVAL, "jxs_action_create: the model has no joints");
+    if (n < 1) return refuse(who, "the model has no joints");
     int bad = -1;
     const int err = jxs_act::table_error(joints, params, n, A, T(0), &bad);
     if (err == jxs_act::kBadWidth)
-      return fail(JXS_EINVAL, "jxs_action_create: A = " + std::to_string(A) + " outside [0, " + std::to_string(JXS_ACT_MAX_WIDTH) + "]");
+      return refuse(who, "A = " + std::to_string(A) + " outside [0, " + std::to_string(JXS_ACT_MAX_WIDTH) + "]");
     if (err != jxs_act::kOk) {
       const char* what = err == jxs_act::kBadMode     ? "unknown mode"
                          : err == jxs_act::kBadColumn ? "column outside [-1, A)"
                          : err == jxs_act::kNotFinite ? "scale, offset, kp or kd not finite in the model's dtype"
                          : err == jxs_act::kBadLimit  ? "action_clip or torque_limit negative, NaN or not finite in the model's dtype"
                                                       : "target_lo above target_hi, NaN or not finite in the model's dtype";
-      return fail(JXS_EINVAL, "jxs_action_create: joint " + std::to_string(bad) + " {" + std::to_string(joints[2 * bad]) + ", " +
-                                  std::to_string(joints[2 * bad + 1]) + "}: " + what);
+      return refuse(who, "joint " + std::to_string(bad) + " {" + std::to_string(joints[2 * bad]) + ", " + std::to_string(joints[2 * bad + 1]) + "}: " + what);
     }
-    if (P.n_rows >= (1 << 26)) return fail(JXS_EINVAL, "jxs_action_create: a state of 2^26 rows or more");
+    if (P.n_rows >= (1 << 26)) return refuse(who, "a state of 2^26 rows or more");
     auto ac = std::make_unique<jxs_action>();
     ac->dtype = model->dtype, ac->A = A, ac->n_rows = P.n_rows, ac->n_joints = n;
     ac->params_at = ((size_t)n * sizeof(int32_t) + 15) / 16 * 16;
@@ -1382,79 +1371,55 @@ int jxs_action_create(jxs_model* model, int A, const int32_t* joints, const doub
       ac->reads_actions = ac->reads_actions || joints[2 * j + 1] >= 0;
       for (int k = 0; k < jxs_act::kParams; ++k) pr[j].v[k] = static_cast<T>(params[jxs_act::kParams * j + k]);
     }
-    JXS_HIP(hipMalloc(&ac->table, host.size()));
-    const hipError_t e = hipMemcpy(ac->table, host.data(), host.size(), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-      (void)hipFree(ac->table);
-      return hip_fail(e, "uploading the action table");
-    }
+    if ((ac->table = upload_table(host, "uploading the action table")) == nullptr) return JXS_ENODEVICE;
     *out = ac.release();
     return JXS_OK;
   });
 }
-int jxs_action_destroy(jxs_action* action) {
-  if (action == nullptr) return JXS_OK;
-  (void)hipFree(action->table);  // (hipFree waits for the launches that may still read the table)
-  delete action;
-  return JXS_OK;
-}
+int jxs_action_destroy(jxs_action* action) { return destroy_table(action); }
 
 int jxs_env_act(jxs_model* model, const jxs_action* action, const void* state, const void* actions, int act_dtype, int64_t act_ld,
                 const void* feed_forward, void* out_tau, int N, void* stream) {
-  if (model == nullptr || action == nullptr || state == nullptr || out_tau == nullptr) return fail(JXS_EINVAL, "jxs_env_act: null argument");
-  if (N <= 0) return fail(JXS_EINVAL, "jxs_env_act: N must be positive");
-  if (act_dtype != JXS_F32 && act_dtype != JXS_F64) return fail(JXS_EINVAL, "jxs_env_act: unknown act_dtype");
-  if (act_dtype != JXS_F32 && act_dtype != model->dtype) return fail(JXS_EINVAL, "jxs_env_act: act_dtype must be JXS_F32 or the model's dtype");
+  const char* const who = "jxs_env_act";
+  if (model == nullptr || action == nullptr || state == nullptr || out_tau == nullptr) return refuse(who, "null argument");
+  if (N <= 0) return refuse(who, "N must be positive");
+  if (act_dtype != JXS_F32 && act_dtype != JXS_F64) return refuse(who, "unknown act_dtype");
+  if (act_dtype != JXS_F32 && act_dtype != model->dtype) return refuse(who, "act_dtype must be JXS_F32 or the model's dtype");
   const jxs_action& ac = *action;
-  if (act_ld < ac.A) return fail(JXS_EINVAL, "jxs_env_act: act_ld = " + std::to_string(act_ld) + " below A = " + std::to_string(ac.A));
-  if (ac.reads_actions && actions == nullptr) return fail(JXS_EINVAL, "jxs_env_act: the table reads action columns, and actions is null");
+  if (act_ld < ac.A) return refuse(who, "act_ld = " + std::to_string(act_ld) + " below A = " + std::to_string(ac.A));
+  if (ac.reads_actions && actions == nullptr) return refuse(who, "the table reads action columns, and actions is null");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const int rc = with_typed(model, [&](auto* mt) {
+  return with_typed(model, [&](auto* mt) {
     using T = typename std::remove_pointer_t<decltype(mt)>::value_type;
     const auto& P = mt->pk.P;
-    if (ac.dtype != model->dtype || ac.n_rows != P.n_rows || ac.n_joints != P.n)
-      return fail(JXS_EINVAL, "jxs_env_act: the action table was created for another state layout or dtype");
-    const int tile = 64 / mt->pk.G;
-    int tile_shift = 0;
-    while ((1 << tile_shift) < tile) ++tile_shift;
-    if (tile <= 0 || (1 << tile_shift) != tile || tile > 64) return fail(JXS_EINVAL, "jxs_env_act: the model's tile does not divide the wave");
-    if (jxs_env::tile_words(P.n_rows, tile) >= (1LL << 30)) return fail(JXS_EINVAL, "jxs_env_act: rows * tile must be below 2^30");
+    if (!table_fits(ac, model->dtype, P)) return refuse(who, "the action table was created for another state layout or dtype");
+    EnvTile t;
+    if (const int rc = env_tile(who, mt->pk.G, P.n_rows, t)) return rc;
+    const int tile = t.tile;
     const size_t ab = act_dtype == JXS_F64 ? 8 : 4;
     const void* act = ac.reads_actions ? actions : nullptr;  // (a tensor the table does not read is not looked at)
     if ((uintptr_t)state % sizeof(T) != 0 || (uintptr_t)out_tau % sizeof(T) != 0 || (uintptr_t)feed_forward % sizeof(T) != 0 || (uintptr_t)act % ab != 0)
-      return fail(JXS_EINVAL, "jxs_env_act: state, actions, feed_forward and out_tau must be aligned to their element type");
+      return refuse(who, "state, actions, feed_forward and out_tau must be aligned to their element type");
     // The widest access that the span of the n joint rows of a tile, the tile span of the state, the places of the q and qd
     // rows in it and the three block addresses allow.  (The humanoid in fp32: 23 x 2 x 4 = 184 bytes, rows at 56 and 288: 8.)
     const int wb = (int)sizeof(T), n = P.n;
     const unsigned long long q_at = (unsigned long long)jxs_act::row_q(n) * tile * wb, qd_at = (unsigned long long)jxs_act::row_qd(n) * tile * wb;
     const int access = std::min(jxs_env::access_bytes((unsigned long long)(uintptr_t)out_tau | (unsigned long long)(uintptr_t)feed_forward, n, tile, wb),
                                 jxs_env::access_bytes((unsigned long long)(uintptr_t)state | q_at | qd_at, P.n_rows, tile, wb));
-    // Environments per wave, E = 2^env_shift with T <= E <= max(T, 32), by the rule of jxs_env_observe: as many as still leave
-    // the chip 8192 waves.  Measured on the humanoid (profiles/env_act.txt): at N = 65 536 a wave of 4, 8 or 16 environments
-    // takes 7.2 .. 7.4 us, one of 2 or 32 about 11 us; at N = 1024 everything up to 8 is one launch interval (3.6 us).
-    int knobs, duo_blocks;
-    debug_knobs(knobs, duo_blocks);  // (reads the environment on the first call of the process)
-    (void)knobs, (void)duo_blocks;
-    const int want = g_act_envs_per_wave.load(std::memory_order_relaxed);
-    int env_shift = tile_shift;
-    const int max_shift = std::max(tile_shift, 5);
-    if (want > 0) {
-      while (env_shift < max_shift && (1 << env_shift) < want) ++env_shift;
-    } else {
-      while (env_shift < max_shift && ((long long)N >> (env_shift + 1)) >= 8192) ++env_shift;
-    }
-    const long long waves = ((long long)N + (1LL << env_shift) - 1) >> env_shift;
-    const dim3 grid((unsigned)((waves + 3) / 4));
-    if (act_dtype == model->dtype)
-      launch_env_act<T, T>(access, grid, s, state, act, (long long)act_ld, ac, feed_forward, out_tau, N, tile_shift, env_shift);
-    else
-      launch_env_act<T, float>(access, grid, s, state, act, (long long)act_ld, ac, feed_forward, out_tau, N, tile_shift, env_shift);
-    return (int)JXS_OK;
+    const int env_shift = jxs_env::env_shift_for(N, t.tile_shift, knob(g_act_envs_per_wave));
+    const unsigned char* tb = static_cast<const unsigned char*>(ac.table);
+    const int32_t* codes = reinterpret_cast<const int32_t*>(tb);
+    const jxs_act::Params<T>* params = reinterpret_cast<const jxs_act::Params<T>*>(tb + ac.params_at);
+    with_io_type<T>(act_dtype == model->dtype, [&](auto a) {
+      using AT = decltype(a);
+      with_access<sizeof(T)>(access, [&](auto width) {
+        hipLaunchKernelGGL((jxs_env_act_kernel<T, AT, decltype(width)::value>), env_grid(env_waves(N, env_shift)), dim3(kEnvBlock), 0, s,
+                           static_cast<const T*>(state), static_cast<const AT*>(act), (long long)act_ld, codes, params,
+                           static_cast<const T*>(feed_forward), static_cast<T*>(out_tau), ac.n_joints, ac.n_rows, N, t.tile_shift, env_shift);
+      });
+    });
+    return launched(who);
   });
-  if (rc != JXS_OK) return rc;
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail(e, "jxs_env_act");
-  return JXS_OK;
 }
 
 int jxs_step(jxs_model* model, const void* state_in, void* state_out, const void* tau, const void* link_forces,
@@ -1691,8 +1656,7 @@ int jxs_gravity_torques(jxs_model* model, const void* state, void* out_tau, int 
   return run(model, L, stream);
 }
 int jxs_debug_reload_env(void) {
-  int k, b;
-  debug_knobs(k, b);  // (the first read happens exactly once)
+  (void)knob(g_knobs);  // (the first read happens exactly once)
   load_knobs();
   return JXS_OK;
 }

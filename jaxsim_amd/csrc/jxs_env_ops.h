@@ -91,4 +91,23 @@ JXS_ENV_HD int access_bytes(unsigned long long address_bits, int rows, int tile,
   return word_bytes;
 }
 
+// Environments per wave of jxs_env_observe and jxs_env_act (host only), E = 2^shift with T <= E <= max(T, 32), T = 2^tile_shift:
+// as many as still leave the chip 8192 waves (256 CUs x 4 SIMDs x 8), so that what a wave reads once (the table, the derived
+// values' prologue) is shared by more environments at large N, while a small batch is spread over as many waves as it has
+// tiles.  `want` > 0 (the launcher's developer knob) asks for at least that many instead, within the same limits.
+// Measured on the humanoid.  The 60-wide observation (profiles/env_observe.txt): at N = 65 536 fastest with 8 environments
+// per wave (about 18.5 / 13 / 10.7 / 11.8 / 14.7 us with 2 / 4 / 8 / 16 / 32), at N = 1024 with one tile per wave (32
+// environments per wave take twice as long).  The torques (profiles/env_act.txt): at N = 65 536 a wave of 4, 8 or 16
+// environments takes 7.2 .. 7.4 us, one of 2 or 32 about 11 us; at N = 1024 everything up to 8 is one launch interval (3.6 us).
+inline int env_shift_for(int N, int tile_shift, int want) {
+  const int max_shift = tile_shift > 5 ? tile_shift : 5;
+  int shift = tile_shift;
+  if (want > 0) {
+    while (shift < max_shift && (1 << shift) < want) ++shift;
+  } else {
+    while (shift < max_shift && ((long long)N >> (shift + 1)) >= 8192) ++shift;
+  }
+  return shift;
+}
+
 }  // namespace jxs_env

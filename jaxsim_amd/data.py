@@ -393,6 +393,45 @@ class JaxSimModelData:
             raise ValueError(
                 f"{what} holds {other.batch_size} environments (tile {other._state.tile}), not {self.batch_size} (tile {self._state.tile})")
 
+    def _check_spec(self, spec, cls, what: str) -> None:
+        """The argument ``what`` must be a ``cls`` (``RandomStateDistribution``, ``ObservationSpec``, ``ActionSpec``) that was
+        built for this object's model layout and dtype."""
+        if not isinstance(spec, cls):
+            raise ValueError(f"{what} must be {'an' if cls.__name__[0] in 'AEIOU' else 'a'} {cls.__name__}, not {type(spec).__name__}")
+        if spec.layout != StateLayout.of(self._model_ref) or spec.layout.n_rows != self._state.rows:
+            raise ValueError(f"{what} was built for another model layout ({spec.layout} != {StateLayout.of(self._model_ref)})")
+        if spec.dtype != self.dtype:
+            raise ValueError(f"{what} was built for dtype {spec.dtype}, not {self.dtype}")
+
+    def _check_block(self, name: str, blk, rows: int) -> None:
+        """The argument ``name`` must be a tiled ``[rows][batch_size]`` ``DeviceArray`` of this object's dtype and tile."""
+        st = self._state
+        if not isinstance(blk, runtime.DeviceArray):
+            raise ValueError(f"{name} must be a runtime.DeviceArray, not {type(blk).__name__}")
+        if blk.shape != (rows, st.cols) or blk.dtype != st.dtype or blk.tile != st.tile:
+            raise ValueError(f"{name} is {blk.shape} {blk.dtype} tile {blk.tile}: expected ({rows}, {st.cols}) {st.dtype} tile {st.tile}")
+
+    def _matrix_arg(self, name: str, m, width: int, *, writable: bool):
+        """``(device pointer, leading dimension, dtype)`` of the argument ``name``, an environment-major ``(batch_size, width)``
+        matrix of float32 or this object's dtype: a ``runtime.DeviceMatrix`` or an object with a 2-D
+        ``__cuda_array_interface__``, used in place.  ``None`` for anything else."""
+        N, dt = self._state.cols, self.dtype
+        if isinstance(m, runtime.DeviceMatrix):
+            if m.shape != (N, width) or m.dtype not in (np.dtype(np.float32), dt):
+                raise ValueError(f"{name} is {m.shape} {m.dtype}: expected ({N}, {width}) float32 or {dt}")
+            return m.ptr, width, m.dtype
+        if hasattr(m, "__cuda_array_interface__"):
+            return runtime.foreign_matrix(m, N, width, tuple({"<f4", dt.str}), writable=writable)
+        return None
+
+    def _result(self, out: runtime.DeviceArray, inplace: bool) -> "JaxSimModelData":
+        """What an operation with an ``inplace`` switch returns: this object, whose buffer ``out`` is and whose cached host
+        copies are stale now, or a new object around ``out``."""
+        if inplace:
+            self._invalidate_caches()
+            return self
+        return JaxSimModelData(self._model_ref, out, self.velocity_representation, self._batched)
+
     def reset_where(self, mask, fresh: "JaxSimModelData", *, inplace: bool = False) -> "JaxSimModelData":
         """Environments whose ``mask`` entry is true take ``fresh``'s state, the others keep theirs -- the reference's
         ``jax.tree.map(lambda a, b: jnp.where(done, a, b), fresh, data)`` under ``vmap``, as one kernel (``jxs_env_select``)
@@ -413,10 +452,7 @@ class JaxSimModelData:
             "jxs_env_select",
         )
         del keep  # (a mask uploaded here goes back to the pool behind the launch, ordered by the stream)
-        if inplace:
-            self._invalidate_caches()
-            return self
-        return JaxSimModelData(self._model_ref, out, self.velocity_representation, self._batched)
+        return self._result(out, inplace)
 
     def reset_random_where(self, mask, dist: "RandomStateDistribution", *, seed: int = 0, draw: int = 0, first_env: int = 0,
                            inplace: bool = False) -> "JaxSimModelData":
@@ -434,13 +470,8 @@ class JaxSimModelData:
         otherwise the block is copied first."""
         from .api.model import _device_model_fast
 
-        if not isinstance(dist, RandomStateDistribution):
-            raise ValueError(f"dist must be a RandomStateDistribution, not {type(dist).__name__}")
+        self._check_spec(dist, RandomStateDistribution, "dist")
         st = self._state
-        if dist.layout != StateLayout.of(self._model_ref) or dist.layout.n_rows != st.rows:
-            raise ValueError(f"dist was built for another model layout ({dist.layout} != {StateLayout.of(self._model_ref)})")
-        if dist.dtype != self.dtype:
-            raise ValueError(f"dist was built for dtype {dist.dtype}, not {self.dtype}")
         seed, draw, first_env = int(seed), int(draw), int(first_env)
         if not (0 <= seed < 2**64 and 0 <= draw < 2**64):
             raise ValueError("seed and draw must fit 64 unsigned bits")
@@ -455,10 +486,7 @@ class JaxSimModelData:
             "jxs_env_randomize",
         )  # fmt: skip
         del keep
-        if inplace:
-            self._invalidate_caches()
-            return self
-        return JaxSimModelData(self._model_ref, out, self.velocity_representation, self._batched)
+        return self._result(out, inplace)
 
     def take(self, indices) -> "JaxSimModelData":
         """A new data object of the ``K`` environments ``indices`` (``jax.tree.map(lambda x: x[indices], data)``), gathered
@@ -497,10 +525,7 @@ class JaxSimModelData:
             "jxs_env_copy",
         )
         del keep
-        if inplace:
-            self._invalidate_caches()
-            return self
-        return JaxSimModelData(self._model_ref, out, self.velocity_representation, self._batched)
+        return self._result(out, inplace)
 
     def env_flags(self) -> runtime.DeviceMask:
         """One byte per environment, on the device (``jxs_env_flags``): bit 0 = some state entry is NaN or infinite,
@@ -534,13 +559,8 @@ class JaxSimModelData:
         wrong ``out``."""
         from .api.model import _device_model_fast
 
-        if not isinstance(spec, ObservationSpec):
-            raise ValueError(f"spec must be an ObservationSpec, not {type(spec).__name__}")
+        self._check_spec(spec, ObservationSpec, "spec")
         st = self._state
-        if spec.layout != StateLayout.of(self._model_ref) or spec.layout.n_rows != st.rows:
-            raise ValueError(f"spec was built for another model layout ({spec.layout} != {StateLayout.of(self._model_ref)})")
-        if spec.dtype != self.dtype:
-            raise ValueError(f"spec was built for dtype {spec.dtype}, not {self.dtype}")
         sources = dict(sources or {})
         unknown = sorted(set(sources) - set(spec.source_names))
         if unknown:
@@ -550,22 +570,15 @@ class JaxSimModelData:
             blk = sources.get(name)
             if blk is None:
                 raise ValueError(f"the spec reads the source {name!r}, which was not given")
-            if not isinstance(blk, runtime.DeviceArray):
-                raise ValueError(f"source {name!r} must be a runtime.DeviceArray, not {type(blk).__name__}")
-            if blk.shape != (rows, st.cols) or blk.dtype != st.dtype or blk.tile != st.tile:
-                raise ValueError(f"source {name!r} is {blk.shape} {blk.dtype} tile {blk.tile}: expected ({rows}, {st.cols}) {st.dtype} tile {st.tile}")
+            self._check_block(f"source {name!r}", blk, rows)
             blocks.append(blk)
         N, D = st.cols, spec.size
         if out is None:
             out = runtime.DeviceMatrix(N, D, spec.out_dtype)
-        if isinstance(out, runtime.DeviceMatrix):
-            if out.shape != (N, D) or out.dtype not in (np.dtype(np.float32), st.dtype):
-                raise ValueError(f"out is {out.shape} {out.dtype}: expected ({N}, {D}) float32 or {st.dtype}")
-            optr, ld, odt = out.ptr, D, out.dtype
-        elif hasattr(out, "__cuda_array_interface__"):
-            optr, ld, odt = runtime.foreign_matrix(out, N, D, tuple({"<f4", st.dtype.str}))
-        else:
+        where = self._matrix_arg("out", out, D, writable=True)
+        if where is None:
             raise ValueError(f"out must be None, a runtime.DeviceMatrix or a 2-D __cuda_array_interface__ object, not {type(out).__name__}")
+        optr, ld, odt = where
         rep = self.velocity_representation if spec.velocity_representation is None else spec.velocity_representation
         dm = _device_model_fast(self._model_ref, self.dtype)
         ptrs = (C.c_void_p * 4)(*[b.ptr for b in blocks])
@@ -583,13 +596,9 @@ class JaxSimModelData:
             if spec.reads_actions:
                 raise ValueError("actions is None, and the spec names action columns")
             return None, None, A, np.dtype(np.float32)
-        if isinstance(actions, runtime.DeviceMatrix):
-            if actions.shape != (N, A) or actions.dtype not in (np.dtype(np.float32), dt):
-                raise ValueError(f"actions is {actions.shape} {actions.dtype}: expected ({N}, {A}) float32 or {dt}")
-            return actions, actions.ptr, A, actions.dtype
-        if hasattr(actions, "__cuda_array_interface__"):
-            ptr, ld, adt = runtime.foreign_matrix(actions, N, A, tuple({"<f4", dt.str}), writable=False)
-            return actions, ptr, ld, adt
+        where = self._matrix_arg("actions", actions, A, writable=False)
+        if where is not None:
+            return (actions, *where)
         a = np.asarray(actions)
         if a.dtype not in (np.dtype(np.float32), dt):
             a = a.astype(dt)
@@ -615,21 +624,12 @@ class JaxSimModelData:
         mis-shaped ``feed_forward`` or ``out``."""
         from .api.model import _device_model_fast
 
-        if not isinstance(spec, ActionSpec):
-            raise ValueError(f"spec must be an ActionSpec, not {type(spec).__name__}")
+        self._check_spec(spec, ActionSpec, "spec")
         st = self._state
-        if spec.layout != StateLayout.of(self._model_ref) or spec.layout.n_rows != st.rows:
-            raise ValueError(f"spec was built for another model layout ({spec.layout} != {StateLayout.of(self._model_ref)})")
-        if spec.dtype != self.dtype:
-            raise ValueError(f"spec was built for dtype {spec.dtype}, not {self.dtype}")
         N, n = st.cols, spec.layout.n_joints
         for name, blk in (("feed_forward", feed_forward), ("out", out)):
-            if blk is None:
-                continue
-            if not isinstance(blk, runtime.DeviceArray):
-                raise ValueError(f"{name} must be a runtime.DeviceArray, not {type(blk).__name__}")
-            if blk.shape != (n, N) or blk.dtype != st.dtype or blk.tile != st.tile:
-                raise ValueError(f"{name} is {blk.shape} {blk.dtype} tile {blk.tile}: expected ({n}, {N}) {st.dtype} tile {st.tile}")
+            if blk is not None:
+                self._check_block(name, blk, n)
         keep, aptr, ld, adt = self._action_tensor(spec, actions)
         if out is None:
             out = runtime.DeviceArray(n, N, st.dtype, tile=st.tile)
@@ -812,7 +812,32 @@ OBS_STATE_ROW, OBS_SOURCE_ROW, OBS_BASE_QUAT_UNIT, OBS_BASE_ROTATION, OBS_BASE_V
 OBS_MAX_WIDTH, OBS_MAX_SOURCES = 4096, 4
 
 
-class ObservationSpec:
+class _SpecTable:
+    """The device table of a spec (``ObservationSpec``: ``jxs_observation``, ``ActionSpec``: ``jxs_action``): one per spec,
+    uploaded at the first use -- one small allocation and a blocking copy -- and freed with the spec.  The table holds
+    nothing of the model; the library checks it against the layout and dtype of the model of every launch, so one table
+    serves every device model of the spec's layout.  A spec gives ``_create(dm, handle)``, which fills ``handle`` through
+    the library's create call or raises, and names the library's destroy call in ``_destroy``."""
+
+    _handle = None
+
+    def _table(self, dm) -> C.c_void_p:
+        if self._handle is None:
+            h = C.c_void_p()
+            self._create(dm, h)
+            self._handle = h
+        return self._handle
+
+    def __del__(self):
+        h, self._handle = self._handle, None
+        if h is not None:
+            try:
+                getattr(_lib.load(), self._destroy)(h)
+            except Exception:
+                pass
+
+
+class ObservationSpec(_SpecTable):
     """What ``JaxSimModelData.observe`` assembles for one model: an ordered list of terms, flattened into ``size`` slots
     ``(kind, source, index)`` with an offset and a scale each (the table of ``jxs_observation_create``).  Built once on the
     host -- no device is needed --, uploaded at the first ``observe``, used for every step of a loop.
@@ -830,7 +855,6 @@ class ObservationSpec:
         self.scale = np.ascontiguousarray(scale, dtype=np.float64)
         self.slices = dict(slices)
         self.source_names, self.source_rows = tuple(source_names), tuple(int(r) for r in source_rows)
-        self._handle = None
 
     @property
     def size(self) -> int:
@@ -945,30 +969,16 @@ class ObservationSpec:
             raise ValueError(f"an observation of {len(slots)} elements: expected 1 .. {OBS_MAX_WIDTH}")
         return ObservationSpec(lay, dt, odt, velocity_representation, slots, offset, scale, slices, src_names, src_rows)
 
-    def _table(self, dm) -> C.c_void_p:
-        """The device table (``jxs_observation``), uploaded at the first use: one small allocation and a blocking copy.  The
-        library checks it against the layout and dtype of the model of every launch, so one table serves every device
-        model of this spec's layout."""
-        if self._handle is None:
-            h = C.c_void_p()
-            rows = (C.c_int32 * 4)(*(list(self.source_rows) + [0] * (4 - len(self.source_rows))))
-            _lib.check(
-                _lib.load().jxs_observation_create(
-                    dm.handle, self.size, self.slots.ctypes.data_as(C.POINTER(C.c_int32)), self.offset.ctypes.data_as(C.POINTER(C.c_double)),
-                    self.scale.ctypes.data_as(C.POINTER(C.c_double)), rows, C.byref(h)),
-                "jxs_observation_create",
-            )  # fmt: skip
-            self._handle = h
-        return self._handle
+    _destroy = "jxs_observation_destroy"
 
-    def __del__(self):
-        h = getattr(self, "_handle", None)
-        if h is not None:
-            self._handle = None
-            try:
-                _lib.load().jxs_observation_destroy(h)
-            except Exception:
-                pass
+    def _create(self, dm, handle) -> None:
+        rows = (C.c_int32 * 4)(*(list(self.source_rows) + [0] * (4 - len(self.source_rows))))
+        _lib.check(
+            _lib.load().jxs_observation_create(
+                dm.handle, self.size, self.slots.ctypes.data_as(C.POINTER(C.c_int32)), self.offset.ctypes.data_as(C.POINTER(C.c_double)),
+                self.scale.ctypes.data_as(C.POINTER(C.c_double)), rows, C.byref(handle)),
+            "jxs_observation_create",
+        )  # fmt: skip
 
 
 # modes of an action-table entry (JXS_ACT_* of include/jaxsim_amd.h) and the order of its eight parameters
@@ -978,7 +988,7 @@ ACT_PARAMS = ("scale", "offset", "kp", "kd", "action_clip", "target_lo", "target
 ACT_MAX_WIDTH = 4096
 
 
-class ActionSpec:
+class ActionSpec(_SpecTable):
     """How ``JaxSimModelData.act`` turns a policy's action tensor into joint torques for one model: one entry per joint of
     the model, ``(mode, column)`` and the eight parameters ``ACT_PARAMS`` (the table of ``jxs_action_create``).  Built once on
     the host -- no device is needed --, uploaded at the first ``act``, used for every sub-step of a loop.
@@ -994,7 +1004,6 @@ class ActionSpec:
         self.width = int(width)
         self.joint_names = tuple(joint_names)
         self.columns = {nm: c for c, nm in enumerate(self.joint_names)}
-        self._handles = {}
 
     @property
     def reads_actions(self) -> bool:
@@ -1128,24 +1137,11 @@ class ActionSpec:
                 raise ValueError(f"joint {names[i]!r}: target limits ({lo}, {hi}): expected lo <= hi, each infinite or finite in {dt.name}")
         return ActionSpec(lay, dt, table, params, A, named)
 
-    def _table(self, dm) -> C.c_void_p:
-        """The device table (``jxs_action``), uploaded at the first use and kept per device model: one small allocation and
-        a blocking copy."""
-        rec = self._handles.get(id(dm))
-        if rec is None:
-            h = C.c_void_p()
-            _lib.check(
-                _lib.load().jxs_action_create(dm.handle, self.width, self.joints.ctypes.data_as(C.POINTER(C.c_int32)),
-                                              self.params.ctypes.data_as(C.POINTER(C.c_double)), C.byref(h)),
-                "jxs_action_create",
-            )  # fmt: skip
-            rec = self._handles[id(dm)] = (dm, h)  # (the device model is kept alive with the table made from it)
-        return rec[1]
+    _destroy = "jxs_action_destroy"
 
-    def __del__(self):
-        handles, self._handles = getattr(self, "_handles", {}), {}
-        for _dm, h in handles.values():
-            try:
-                _lib.load().jxs_action_destroy(h)
-            except Exception:
-                pass
+    def _create(self, dm, handle) -> None:
+        _lib.check(
+            _lib.load().jxs_action_create(dm.handle, self.width, self.joints.ctypes.data_as(C.POINTER(C.c_int32)),
+                                          self.params.ctypes.data_as(C.POINTER(C.c_double)), C.byref(handle)),
+            "jxs_action_create",
+        )  # fmt: skip

@@ -93,6 +93,8 @@ int jxs_emul_env_access_bytes(unsigned long long address_bits, int rows, int til
   return jxs_env::access_bytes(address_bits, rows, tile, word_bytes);
 }
 
+int jxs_emul_env_shift_for(int N, int tile_shift, int want) { return jxs_env::env_shift_for(N, tile_shift, want); }
+
 long long jxs_emul_env_block_words(int rows, long long N, int tile) { return jxs_env::block_words(rows, N, tile); }
 
 long long jxs_emul_env_word_of(long long env, int row, int rows, int tile) { return jxs_env::word_of(env, row, rows, tile); }

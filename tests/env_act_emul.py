@@ -2,54 +2,21 @@
 (tests/emul/jxs_emul_env_act.cpp), which runs ``jxs_act::torque_word`` of jaxsim_amd/csrc/jxs_env_act.h over every word of
 the tiled torque block.
 
-Builds ``tests/emul/libjxs_emul_env_act.so`` with g++ on demand (a second or two).
+The library is the one of tests/env_emul_lib.py.
 """
 
 from __future__ import annotations
 
 import ctypes as C
-import os
-import pathlib
-import subprocess
 
 import numpy as np
+from env_emul_lib import _ptr, declare, lib
 
-_HERE = pathlib.Path(__file__).resolve().parent
-_SRC = _HERE / "emul" / "jxs_emul_env_act.cpp"
-_SO = _HERE / "emul" / "libjxs_emul_env_act.so"
-_CSRC = _HERE.parent / "jaxsim_amd" / "csrc"
-_HEADERS = (_CSRC / "jxs_env_act.h", _CSRC / "jxs_env_observe.h", _CSRC / "jxs_env_random.h", _CSRC / "jxs_env_ops.h")
-
-
-def build(force: bool = False) -> pathlib.Path:
-    if force or not _SO.exists() or any(d.stat().st_mtime > _SO.stat().st_mtime for d in (_SRC, *_HEADERS)):
-        tmp = _SO.with_suffix(f".tmp{os.getpid()}.so")
-        cmd = ["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-Wall", "-ffp-contract=off", f"-I{_CSRC}", str(_SRC), "-o", str(tmp)]
-        subprocess.run(cmd, check=True)
-        os.replace(tmp, _SO)
-    return _SO
-
-
-_emul = None
-
-
-def lib():
-    global _emul
-    if _emul is None:
-        _emul = C.CDLL(str(build()))
-        vp, i, ll, d = C.c_void_p, C.c_int, C.c_longlong, C.c_double
-        _emul.jxs_emul_act_table_error.restype = i
-        _emul.jxs_emul_act_table_error.argtypes = [vp, vp, ll, ll, i, C.POINTER(i)]
-        for name, args in (("finite_ok", [d, i]), ("limit_ok", [d, i]), ("targets_ok", [d, d, i]), ("pack_roundtrip", [i, i])):
-            f = getattr(_emul, f"jxs_emul_act_{name}")
-            f.restype, f.argtypes = i, args
-        _emul.jxs_emul_env_act.restype = i
-        _emul.jxs_emul_env_act.argtypes = [vp, vp, ll, i, vp, vp, i, i, vp, vp, i, i, i, i]
-    return _emul
-
-
-def _ptr(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
+_vp, _i, _ll, _d = C.c_void_p, C.c_int, C.c_longlong, C.c_double
+declare(("jxs_emul_act_table_error", _i, [_vp, _vp, _ll, _ll, _i, C.POINTER(_i)]),
+        ("jxs_emul_act_finite_ok", _i, [_d, _i]), ("jxs_emul_act_limit_ok", _i, [_d, _i]),
+        ("jxs_emul_act_targets_ok", _i, [_d, _d, _i]), ("jxs_emul_act_pack_roundtrip", _i, [_i, _i]),
+        ("jxs_emul_env_act", _i, [_vp, _vp, _ll, _i, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i]))  # fmt: skip
 
 
 def _table(joints, params):

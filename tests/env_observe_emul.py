@@ -2,55 +2,21 @@
 (tests/emul/jxs_emul_env_observe.cpp), which runs ``jxs_obs::slot_value`` of jaxsim_amd/csrc/jxs_env_observe.h over every
 word of the tensor.
 
-Builds ``tests/emul/libjxs_emul_env_observe.so`` with g++ on demand (a second or two).
+The library is the one of tests/env_emul_lib.py.
 """
 
 from __future__ import annotations
 
 import ctypes as C
-import os
-import pathlib
-import subprocess
 
 import numpy as np
+from env_emul_lib import _ptr, declare, lib
 
-_HERE = pathlib.Path(__file__).resolve().parent
-_SRC = _HERE / "emul" / "jxs_emul_env_observe.cpp"
-_SO = _HERE / "emul" / "libjxs_emul_env_observe.so"
-_CSRC = _HERE.parent / "jaxsim_amd" / "csrc"
-_HEADERS = (_CSRC / "jxs_env_observe.h", _CSRC / "jxs_env_random.h", _CSRC / "jxs_env_ops.h")
-
-
-def build(force: bool = False) -> pathlib.Path:
-    if force or not _SO.exists() or any(d.stat().st_mtime > _SO.stat().st_mtime for d in (_SRC, *_HEADERS)):
-        tmp = _SO.with_suffix(f".tmp{os.getpid()}.so")
-        cmd = ["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-Wall", "-ffp-contract=off", f"-I{_CSRC}", str(_SRC), "-o", str(tmp)]
-        subprocess.run(cmd, check=True)
-        os.replace(tmp, _SO)
-    return _SO
-
-
-_emul = None
-
-
-def lib():
-    global _emul
-    if _emul is None:
-        _emul = C.CDLL(str(build()))
-        vp, i, ll = C.c_void_p, C.c_int, C.c_longlong
-        _emul.jxs_emul_observe_table_error.restype = i
-        _emul.jxs_emul_observe_table_error.argtypes = [vp, ll, i, vp, C.POINTER(i)]
-        _emul.jxs_emul_observe_affine_ok.restype = i
-        _emul.jxs_emul_observe_affine_ok.argtypes = [C.c_double, i]
-        _emul.jxs_emul_observe_derived_used.restype = C.c_uint
-        _emul.jxs_emul_observe_derived_used.argtypes = [vp, i, i]
-        _emul.jxs_emul_env_observe.restype = i
-        _emul.jxs_emul_env_observe.argtypes = [vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, vp, ll, i, i]
-    return _emul
-
-
-def _ptr(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
+_vp, _i, _ll = C.c_void_p, C.c_int, C.c_longlong
+declare(("jxs_emul_observe_table_error", _i, [_vp, _ll, _i, _vp, C.POINTER(_i)]),
+        ("jxs_emul_observe_affine_ok", _i, [C.c_double, _i]),
+        ("jxs_emul_observe_derived_used", C.c_uint, [_vp, _i, _i]),
+        ("jxs_emul_env_observe", _i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _ll, _i, _i]))  # fmt: skip
 
 
 def _slots(slots) -> np.ndarray:

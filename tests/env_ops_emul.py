@@ -1,55 +1,23 @@
 """TEST INFRASTRUCTURE: ctypes binding of the host harness of the per-environment operations
 (tests/emul/jxs_emul_env_ops.cpp), which runs the index functions of jaxsim_amd/csrc/jxs_env_ops.h over every word.
-
-Builds ``tests/emul/libjxs_emul_env_ops.so`` with g++ on demand (a second or two).
+The library is the one of tests/env_emul_lib.py.
 """
 
 from __future__ import annotations
 
 import ctypes as C
-import os
-import pathlib
-import subprocess
 
 import numpy as np
+from env_emul_lib import _ptr, declare, lib
 
-_HERE = pathlib.Path(__file__).resolve().parent
-_SRC = _HERE / "emul" / "jxs_emul_env_ops.cpp"
-_SO = _HERE / "emul" / "libjxs_emul_env_ops.so"
-_ROOT = _HERE.parent
-_HEADER = _ROOT / "jaxsim_amd" / "csrc" / "jxs_env_ops.h"
-
-
-def build(force: bool = False) -> pathlib.Path:
-    if force or not _SO.exists() or any(d.stat().st_mtime > _SO.stat().st_mtime for d in (_SRC, _HEADER)):
-        tmp = _SO.with_suffix(f".tmp{os.getpid()}.so")
-        cmd = ["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-Wall", f"-I{_HEADER.parent}", str(_SRC), "-o", str(tmp)]
-        subprocess.run(cmd, check=True)
-        os.replace(tmp, _SO)
-    return _SO
-
-
-_emul = None
-
-
-def lib():
-    global _emul
-    if _emul is None:
-        _emul = C.CDLL(str(build()))
-        vp, i, ll = C.c_void_p, C.c_int, C.c_longlong
-        for name, res, argtypes in (("jxs_emul_env_select", i, [vp, vp, vp, vp, i, i, i, i]),
-                                    ("jxs_emul_env_copy", i, [vp, i, i, vp, vp, i, i, vp, i, i, i]),
-                                    ("jxs_emul_env_flags", i, [vp, i, i, i, i, i, vp]),
-                                    ("jxs_emul_env_access_bytes", i, [C.c_ulonglong, i, i, i]),
-                                    ("jxs_emul_env_block_words", ll, [i, ll, i]),
-                                    ("jxs_emul_env_word_of", ll, [ll, i, i, i])):  # fmt: skip
-            getattr(_emul, name).restype = res
-            getattr(_emul, name).argtypes = argtypes
-    return _emul
-
-
-def _ptr(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
+_vp, _i, _ll = C.c_void_p, C.c_int, C.c_longlong
+declare(("jxs_emul_env_select", _i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i]),
+        ("jxs_emul_env_copy", _i, [_vp, _i, _i, _vp, _vp, _i, _i, _vp, _i, _i, _i]),
+        ("jxs_emul_env_flags", _i, [_vp, _i, _i, _i, _i, _i, _vp]),
+        ("jxs_emul_env_access_bytes", _i, [C.c_ulonglong, _i, _i, _i]),
+        ("jxs_emul_env_shift_for", _i, [_i, _i, _i]),
+        ("jxs_emul_env_block_words", _ll, [_i, _ll, _i]),
+        ("jxs_emul_env_word_of", _ll, [_ll, _i, _i, _i]))  # fmt: skip
 
 
 def select(mask, a: np.ndarray, b: np.ndarray, rows: int, N: int, T: int, *, out: np.ndarray | None = None) -> np.ndarray:
@@ -79,3 +47,7 @@ def flags(state: np.ndarray, rows: int, row_quat: int, N: int, T: int) -> np.nda
 
 def access_bytes(address_bits: int, rows: int, T: int, word_bytes: int) -> int:
     return lib().jxs_emul_env_access_bytes(address_bits, rows, T, word_bytes)
+
+
+def env_shift_for(N: int, tile_shift: int, want: int = 0) -> int:
+    return lib().jxs_emul_env_shift_for(N, tile_shift, want)

@@ -1,53 +1,20 @@
 """TEST INFRASTRUCTURE: ctypes binding of the host harness of the random reset (tests/emul/jxs_emul_env_random.cpp),
 which runs the functions of jaxsim_amd/csrc/jxs_env_random.h over every word of a block.
 
-Builds ``tests/emul/libjxs_emul_env_random.so`` with g++ on demand (a second or two).
+The library is the one of tests/env_emul_lib.py.
 """
 
 from __future__ import annotations
 
 import ctypes as C
-import os
-import pathlib
-import subprocess
 
 import numpy as np
+from env_emul_lib import _ptr, declare, lib
 
-_HERE = pathlib.Path(__file__).resolve().parent
-_SRC = _HERE / "emul" / "jxs_emul_env_random.cpp"
-_SO = _HERE / "emul" / "libjxs_emul_env_random.so"
-_CSRC = _HERE.parent / "jaxsim_amd" / "csrc"
-_HEADERS = (_CSRC / "jxs_env_random.h", _CSRC / "jxs_env_ops.h")
-
-
-def build(force: bool = False) -> pathlib.Path:
-    if force or not _SO.exists() or any(d.stat().st_mtime > _SO.stat().st_mtime for d in (_SRC, *_HEADERS)):
-        tmp = _SO.with_suffix(f".tmp{os.getpid()}.so")
-        cmd = ["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-Wall", "-ffp-contract=off", f"-I{_CSRC}", str(_SRC), "-o", str(tmp)]
-        subprocess.run(cmd, check=True)
-        os.replace(tmp, _SO)
-    return _SO
-
-
-_emul = None
-
-
-def lib():
-    global _emul
-    if _emul is None:
-        _emul = C.CDLL(str(build()))
-        vp, i, u64 = C.c_void_p, C.c_int, C.c_uint64
-        _emul.jxs_emul_philox4x32_10.restype = None
-        _emul.jxs_emul_philox4x32_10.argtypes = [vp, vp, vp]
-        _emul.jxs_emul_env_randomize.restype = i
-        _emul.jxs_emul_env_randomize.argtypes = [vp, vp, i, i, i, i, i, i, vp, u64, u64, C.c_longlong, i]
-        _emul.jxs_emul_env_random_variables.restype = i
-        _emul.jxs_emul_env_random_variables.argtypes = [i]
-    return _emul
-
-
-def _ptr(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
+_vp, _i, _u64 = C.c_void_p, C.c_int, C.c_uint64
+declare(("jxs_emul_philox4x32_10", None, [_vp, _vp, _vp]),
+        ("jxs_emul_env_randomize", _i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _u64, _u64, C.c_longlong, _i]),
+        ("jxs_emul_env_random_variables", _i, [_i]))  # fmt: skip
 
 
 def philox(ctr, key) -> tuple:

@@ -208,6 +208,38 @@ def test_act_equals_the_restatement_fed_from_the_host_properties(models, dtype):
     assert_same_bits(data.act(still, None).to_host(), ref.act(q, qd, still.joints, still.params, None), "hold everything")
 
 
+def test_one_spec_serves_two_device_models_of_one_layout_with_one_table(models, monkeypatch):
+    """One ``ActionSpec`` used on two ``JaxSimModel`` objects built separately from the same description, hence on two device
+    models of one layout: the torque block is, bit for bit, that of a spec per model, and the shared spec uploads exactly one
+    table.  The cartpole, the smallest jointed model here, with N = 3: a last tile with padding columns."""
+    import jaxsim_amd as ja
+    from jaxsim_amd import robots
+
+    dtype, N = np.float32, 3
+    first, second = (ja.JaxSimModel.build_from_model_description(robots.cartpole_urdf()) for _ in range(2))
+    dms = [runtime.device_model(m, dtype) for m in (first, second)]
+    assert first is not second and dms[0] is not dms[1]
+    assert N % dms[0].layout.tile != 0
+    blk = helpers.odata_to_block(first, models.random_data("cartpole", N, seed=7, dtype=dtype))
+    actions = DeviceMatrix.from_host(np.random.default_rng(5).normal(0, 1.2, (N, first.dofs())).astype(np.float32))
+
+    def spec_of(model):
+        return js.data.ActionSpec.build(model, dtype=dtype, kp=30.0, kd=1.5, scale=0.5, action_clip=1.0, torque_limit=4.0)
+
+    lib, created = _lib.load(), []
+    create = lib.jxs_action_create
+    monkeypatch.setattr(lib, "jxs_action_create", lambda *args: created.append(args) or create(*args))
+    shared = spec_of(first)
+    data = [js.data.JaxSimModelData.from_state_block(m, blk) for m in (first, second)]
+    got = [d.act(shared, actions).to_host_raw() for d in data]
+    assert len(created) == 1, "the shared spec uploaded more than one table"
+    for k, (m, d) in enumerate(zip((first, second), data)):
+        want = d.act(spec_of(m), actions).to_host_raw()
+        assert np.isfinite(want).all() and (want != 0).any()
+        assert_same_bits(got[k], want, f"the shared spec on model {k} against a spec of its own")
+    assert len(created) == 3
+
+
 @pytest.mark.parametrize("second_stream", [False, True], ids=["default-stream", "second-stream"])
 def test_control_steps_equals_the_loop_through_the_host(models, second_stream):
     """Five policy steps of ``control_steps`` with decimation 2 (on a second stream nothing synchronises inside), against the

@@ -203,6 +203,25 @@ def test_access_width_follows_the_tile_span_and_the_addresses():
     assert emul.lib().jxs_emul_env_word_of(N - 1, rows - 1, rows, T) == int(ref.word_index(N - 1, rows - 1, rows, T))
 
 
+# The rule of jxs_env::env_shift_for, from which the expected values below are derived (not measured): the shift starts at
+# tile_shift and never passes max(tile_shift, 5); with a knob it grows until 2^shift >= knob, without one while
+# N >> (shift + 1) >= 8192, that is while waves of twice as many environments would still number 8192.
+@pytest.mark.parametrize("want,tile_shift,N,expected", [
+    (0, 1, 1024, 1), (0, 1, 32767, 1), (0, 1, 32768, 2), (0, 1, 65536, 3), (0, 1, 2**20, 5), (0, 4, 65536, 4), (0, 4, 2**19, 5), (0, 6, 2**30, 6),
+    (3, 1, None, 2), (1, 1, None, 1), (64, 1, None, 5), (8, 4, None, 4),
+])  # fmt: skip
+def test_environments_per_wave_follow_the_batch_size_or_the_knob(want, tile_shift, N, expected):
+    for n in (1, 1024, 65536, 2**20, 2**31 - 1) if N is None else (N,):  # (a knob decides whatever the batch size)
+        assert emul.env_shift_for(n, tile_shift, want) == expected, n
+
+
+def test_environments_per_wave_stay_between_a_tile_and_the_larger_of_a_tile_and_32():
+    for tile_shift in range(7):
+        for want in (0, 1, 2, 5, 32, 33, 1000):
+            for N in (1, 2, 63, 8191, 8192, 16383, 16384, 2**15 + 1, 2**17, 2**18 - 1, 2**19, 2**24, 2**30, 2**31 - 1):
+                assert tile_shift <= emul.env_shift_for(N, tile_shift, want) <= max(tile_shift, 5), (N, tile_shift, want)
+
+
 # ---- the C ABI refuses bad arguments without a device ---------------------------------------------------------------
 @pytest.fixture(scope="module")
 def lib():

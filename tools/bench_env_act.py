@@ -23,7 +23,6 @@ import argparse
 import ctypes as C
 import os
 import sys
-import time
 
 import numpy as np
 
@@ -31,6 +30,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import bench  # noqa: E402
+from env_timing import set_envs_per_wave, timed, wall  # noqa: E402
 import jaxsim_amd.api as js  # noqa: E402
 import policy_kernel  # noqa: E402  (the stand-in for a user's own PD kernel)
 from jaxsim_amd import _lib, runtime  # noqa: E402
@@ -50,44 +50,6 @@ runtime.set_stream(stream)
 model = bench.build_model(args.model)
 dtype = np.float32
 F32 = _lib.dtype_code(dtype)
-
-
-def timed(name, call, reps):
-    """us per launch: HIP events around `reps` launches, after 20 warm-up launches; the median of 5 windows."""
-    for _ in range(20):
-        _lib.check(call(), name)
-    stream.synchronize()
-    windows = []
-    for _ in range(5):
-        e0, e1 = runtime.Event(), runtime.Event()
-        e0.record(stream)
-        for _ in range(reps):
-            _lib.check(call(), name)
-        e1.record(stream)
-        stream.synchronize()
-        windows.append(e0.elapsed_ms(e1) / reps * 1e3)
-    return float(np.median(windows)), float(min(windows)), float(max(windows))
-
-
-def wall(loop, repeats=3):
-    """Seconds of `loop()` including the device synchronisation behind it; the median of `repeats` after one warm-up."""
-    loop()
-    stream.synchronize()
-    out = []
-    for _ in range(repeats):
-        t0 = time.perf_counter()
-        loop()
-        stream.synchronize()
-        out.append(time.perf_counter() - t0)
-    return float(np.median(out))
-
-
-def set_envs_per_wave(value):
-    if not value:
-        os.environ.pop("JXS_ACT_ENVS_PER_WAVE", None)
-    else:
-        os.environ["JXS_ACT_ENVS_PER_WAVE"] = str(value)
-    _lib.check(lib.jxs_debug_reload_env(), "jxs_debug_reload_env")
 
 
 print(f"# action-to-torque law, {args.model} synthetic humanoid, fp32, {args.reps} launches per figure (median [min .. max] of 5 windows), HIP events on the launch stream")
@@ -147,18 +109,18 @@ for N in args.envs:
             cases.append((f"(b) act with feed-forward, {e} environments per wave", e, act(sp, ff)))
     ref_c = ref_e = None
     for name, epw, call in cases:
-        set_envs_per_wave(epw)
-        us, lo, hi = timed(name, call, args.reps)
+        set_envs_per_wave("JXS_ACT_ENVS_PER_WAVE", epw)
+        us, lo, hi = timed(stream, name, call, args.reps)
         ref_c = us if ref_c is None else ref_c
         ref_e = us if ref_e is None and name.startswith("(e)") else ref_e
         vs_e = "" if ref_e is None else f"{us / ref_e:7.2f}"
         print(f"  {name:74s} {us:10.2f} {f'[{lo:.2f} .. {hi:.2f}]':>20s} {N / us:9.1f} {us / ref_c:7.2f} {vs_e:>7s}", flush=True)
-    set_envs_per_wave(0)
+    set_envs_per_wave("JXS_ACT_ENVS_PER_WAVE", 0)
     # per step: the step alone against act + step, both in place on a copy of the state (restored before each figure)
     for name, call in (("jxs_step in place with a torque block", step_only), ("act + jxs_step in place", act_and_step)):
         _lib.check(lib.jxs_memcpy_d2d(vp(work.ptr), sp, st.nbytes, h), "jxs_memcpy_d2d")
         _lib.check(lib.jxs_memset(vp(tau.ptr), 0, tau.nbytes, h), "jxs_memset")
-        us, lo, hi = timed(name, call, args.reps)
+        us, lo, hi = timed(stream, name, call, args.reps)
         print(f"  {name:74s} {us:10.2f} {f'[{lo:.2f} .. {hi:.2f}]':>20s} {N / us:9.1f} {us / ref_c:7.2f} {us / ref_e:7.2f}", flush=True)
 
     # (f) the host route to the same torques: one download of the block per property, NumPy, the upload
@@ -171,8 +133,8 @@ for N in args.envs:
         t = np.clip(kp * (np.clip(a_h, -1, 1) * half - q) - kd * qd, -80, 80)
         return runtime.DeviceArray.from_host(np.ascontiguousarray(t.T), tile=tile)
 
-    t = wall(host_torques) * 1e6
+    t = wall(stream, host_torques) * 1e6
     print(f"  {'(f) host properties + NumPy + upload (wall clock)':74s} {t:10.1f} {'':>20s} {N / t:9.3f} {t / ref_c:7.1f} {t / ref_e:7.1f}", flush=True)
     reps = 200
-    t = wall(lambda: [data.act(spec, actions, out=tau) for _ in range(reps)]) / reps * 1e6
+    t = wall(stream, lambda: [data.act(spec, actions, out=tau) for _ in range(reps)]) / reps * 1e6
     print(f"  {'(a) data.act(spec, actions, out=) through Python (wall clock)':74s} {t:10.1f} {'':>20s} {N / t:9.3f} {t / ref_c:7.2f} {t / ref_e:7.2f}", flush=True)

@@ -19,12 +19,12 @@ import argparse
 import ctypes as C
 import os
 import sys
-import time
 
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench  # noqa: E402
+from env_timing import set_envs_per_wave, timed, wall  # noqa: E402
 import jaxsim_amd as ja  # noqa: E402
 import jaxsim_amd.api as js  # noqa: E402
 from jaxsim_amd import _lib, runtime  # noqa: E402
@@ -43,44 +43,6 @@ runtime.set_stream(stream)
 model = bench.build_model(args.model)
 dtype = np.float32
 F32 = _lib.dtype_code(dtype)
-
-
-def timed(name, call, reps):
-    """us per launch: HIP events around `reps` launches, after 20 warm-up launches; the median of 5 windows."""
-    for _ in range(20):
-        _lib.check(call(), name)
-    stream.synchronize()
-    windows = []
-    for _ in range(5):
-        e0, e1 = runtime.Event(), runtime.Event()
-        e0.record(stream)
-        for _ in range(reps):
-            _lib.check(call(), name)
-        e1.record(stream)
-        stream.synchronize()
-        windows.append(e0.elapsed_ms(e1) / reps * 1e3)
-    return float(np.median(windows)), float(min(windows)), float(max(windows))
-
-
-def wall(loop, repeats=3):
-    """Seconds of `loop()` including the device synchronisation behind it; the median of `repeats` after one warm-up."""
-    loop()
-    stream.synchronize()
-    out = []
-    for _ in range(repeats):
-        t0 = time.perf_counter()
-        loop()
-        stream.synchronize()
-        out.append(time.perf_counter() - t0)
-    return float(np.median(out))
-
-
-def set_envs_per_wave(value):
-    if value is None:
-        os.environ.pop("JXS_OBSERVE_ENVS_PER_WAVE", None)
-    else:
-        os.environ["JXS_OBSERVE_ENVS_PER_WAVE"] = str(value)
-    _lib.check(lib.jxs_debug_reload_env(), "jxs_debug_reload_env")
 
 
 PROPRIO = ["joint_positions", "joint_velocities", "base_orientation", "base_velocity", "projected_gravity", "base_height"]
@@ -123,13 +85,13 @@ for N in args.envs:
             cases.append((f"(b) observe, 84 wide, {e} environments per wave", e, observe(spec_b, out_b, src_b)))
     ref_c = ref_d = None
     for name, knob, call in cases:
-        set_envs_per_wave(knob)
-        us, lo, hi = timed(name, call, args.reps)
+        set_envs_per_wave("JXS_OBSERVE_ENVS_PER_WAVE", knob)
+        us, lo, hi = timed(stream, name, call, args.reps)
         ref_c = us if ref_c is None else ref_c
         ref_d = us if ref_d is None and name.startswith("(d)") else ref_d
         vs_d = "" if ref_d is None else f"{us / ref_d:7.2f}"
         print(f"  {name:66s} {us:10.2f} {f'[{lo:.2f} .. {hi:.2f}]':>20s} {N / us:9.1f} {us / ref_c:7.2f} {vs_d:>7s}", flush=True)
-    set_envs_per_wave(None)
+    set_envs_per_wave("JXS_OBSERVE_ENVS_PER_WAVE", None)
 
     # (e) the host path to the same 60 numbers per environment: one download of the block, the properties, the concatenation
     def host_observation():
@@ -139,10 +101,10 @@ for N in args.envs:
         R = data.base_transform[:, :3, :3]
         return np.concatenate([data.joint_positions, data.joint_velocities, data.base_orientation, v, -R[:, 2, :], data.base_position[:, 2:3]], axis=1)
 
-    t = wall(host_observation) * 1e6
+    t = wall(stream, host_observation) * 1e6
     print(f"  {'(e) host properties + NumPy concatenation (wall clock)':66s} {t:10.1f} {'':>20s} {N / t:9.3f} {t / ref_c:7.1f} {t / ref_d:7.1f}", flush=True)
     reps = 200
-    t = wall(lambda: [data.observe(spec_a, out=out_a) for _ in range(reps)]) / reps * 1e6
+    t = wall(stream, lambda: [data.observe(spec_a, out=out_a) for _ in range(reps)]) / reps * 1e6
     print(f"  {'(a) data.observe(spec, out=) through Python (wall clock)':66s} {t:10.1f} {'':>20s} {N / t:9.3f} {t / ref_c:7.2f} {t / ref_d:7.2f}", flush=True)
     got, want = out_a.to_host(), host_observation()
     print(f"#   (largest difference between (a) and (e): {float(np.abs(got.astype(np.float64) - want).max()):.2e})")

@@ -15,12 +15,12 @@ import argparse
 import ctypes as C
 import os
 import sys
-import time
 
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench  # noqa: E402
+from env_timing import timed, wall  # noqa: E402
 import jaxsim_amd.api as js  # noqa: E402
 from jaxsim_amd import _lib, runtime  # noqa: E402
 from jaxsim_amd.model import VelRepr  # noqa: E402
@@ -39,36 +39,6 @@ runtime.set_stream(stream)
 model = bench.build_model(args.model)
 dtype = np.float32
 F32 = _lib.dtype_code(dtype)
-
-
-def timed(name, call, reps):
-    """us per launch: HIP events around `reps` launches, after 20 warm-up launches; the median of 5 windows."""
-    for _ in range(20):
-        _lib.check(call(), name)
-    stream.synchronize()
-    windows = []
-    for _ in range(5):
-        e0, e1 = runtime.Event(), runtime.Event()
-        e0.record(stream)
-        for _ in range(reps):
-            _lib.check(call(), name)
-        e1.record(stream)
-        stream.synchronize()
-        windows.append(e0.elapsed_ms(e1) / reps * 1e3)
-    return float(np.median(windows)), float(min(windows)), float(max(windows))
-
-
-def wall(loop, repeats=3):
-    """Seconds of `loop()` including the device synchronisation behind it; the median of `repeats` after one warm-up."""
-    loop()
-    stream.synchronize()
-    out = []
-    for _ in range(repeats):
-        t0 = time.perf_counter()
-        loop()
-        stream.synchronize()
-        out.append(time.perf_counter() - t0)
-    return float(np.median(out))
 
 
 print(f"# per-environment operations, {args.model} synthetic humanoid, fp32, {args.reps} launches per figure (median [min .. max] of 5 windows), HIP events on the launch stream")
@@ -110,7 +80,7 @@ for N in args.envs:
     ]
     d2d = None
     for name, call in cases:
-        us, lo, hi = timed(name, call, args.reps)
+        us, lo, hi = timed(stream, name, call, args.reps)
         d2d = us if d2d is None else d2d
         print(f"  {name:58s} {us:10.2f} {f'[{lo:.2f} .. {hi:.2f}]':>20s} {N / us:9.1f} {us / d2d:7.2f}", flush=True)
 
@@ -126,7 +96,7 @@ for N in args.envs:
                                 base_angular_velocity=pick["base_angular_velocity"], base_position=pick["base_position"],
                                 contact_state={"tangential_deformation": pick["tangential_deformation"]})  # fmt: skip
 
-    t = wall(host_reset) * 1e6
+    t = wall(stream, host_reset) * 1e6
     print(f"  {'data.replace round trip of the 1 % reset (host, wall clock)':58s} {t:10.1f} {'':>20s} {N / t:9.3f} {t / d2d:7.0f}", flush=True)
 
     # loops through the Python API, wall clock: the bare step loop and the episode loop
@@ -142,7 +112,7 @@ for N in args.envs:
             js.model.step(model, run, inplace=True)
             run.reset_where(run.env_flags(), fresh, inplace=True)
 
-    t_bare, t_epi = wall(bare), wall(episode)
+    t_bare, t_epi = wall(stream, bare), wall(stream, episode)
     print(f"  {f'loop of {steps}: step(inplace=True)':58s} {t_bare / steps * 1e6:10.2f} {'':>20s} {N * steps / t_bare / 1e6:9.1f}")
     print(f"  {f'loop of {steps}: step + env_flags + reset_where(inplace=True)':58s} {t_epi / steps * 1e6:10.2f} {'':>20s} {N * steps / t_epi / 1e6:9.1f}", flush=True)
     bad = int(run.nonfinite_mask().sum())

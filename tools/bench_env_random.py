@@ -14,12 +14,12 @@ import argparse
 import ctypes as C
 import os
 import sys
-import time
 
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench  # noqa: E402
+from env_timing import timed, wall  # noqa: E402
 import jaxsim_amd.api as js  # noqa: E402
 from jaxsim_amd import _lib, runtime  # noqa: E402
 
@@ -36,36 +36,6 @@ runtime.set_stream(stream)
 model = bench.build_model(args.model)
 dtype = np.float32
 F32 = _lib.dtype_code(dtype)
-
-
-def timed(name, call, reps):
-    """us per launch: HIP events around `reps` launches, after 20 warm-up launches; the median of 5 windows."""
-    for _ in range(20):
-        _lib.check(call(), name)
-    stream.synchronize()
-    windows = []
-    for _ in range(5):
-        e0, e1 = runtime.Event(), runtime.Event()
-        e0.record(stream)
-        for _ in range(reps):
-            _lib.check(call(), name)
-        e1.record(stream)
-        stream.synchronize()
-        windows.append(e0.elapsed_ms(e1) / reps * 1e3)
-    return float(np.median(windows)), float(min(windows)), float(max(windows))
-
-
-def wall(loop, repeats=3):
-    """Seconds of `loop()` including the device synchronisation behind it; the median of `repeats` after one warm-up."""
-    loop()
-    stream.synchronize()
-    out = []
-    for _ in range(repeats):
-        t0 = time.perf_counter()
-        loop()
-        stream.synchronize()
-        out.append(time.perf_counter() - t0)
-    return float(np.median(out))
 
 
 print(f"# random resets, {args.model} synthetic humanoid, fp32, {args.reps} launches per figure (median [min .. max] of 5 windows), HIP events on the launch stream")
@@ -110,7 +80,7 @@ for N in args.envs:
     ]
     d2d = None
     for name, call in cases:
-        us, lo, hi = timed(name, call, args.reps)
+        us, lo, hi = timed(stream, name, call, args.reps)
         d2d = us if d2d is None else d2d
         print(f"  {name:62s} {us:10.2f} {f'[{lo:.2f} .. {hi:.2f}]':>20s} {N / us:9.1f} {us / d2d:7.2f}", flush=True)
 
@@ -121,7 +91,7 @@ for N in args.envs:
         seed[0] += 1
         data.reset_where(sparse, js.data.random_model_data(model, batch_size=N, seed=seed[0], dtype=dtype), inplace=True)
 
-    t = wall(host_reset) * 1e6
+    t = wall(stream, host_reset) * 1e6
     print(f"  {'host random_model_data + reset_where of the 1 % reset (wall clock)':62s} {t:10.1f} {'':>20s} {N / t:9.3f} {t / d2d:7.0f}", flush=True)
 
     def device_reset():
@@ -129,7 +99,7 @@ for N in args.envs:
         data.reset_random_where(sparse, dist, draw=seed[0], inplace=True)
 
     reps = 200
-    t = wall(lambda: [device_reset() for _ in range(reps)]) / reps * 1e6
+    t = wall(stream, lambda: [device_reset() for _ in range(reps)]) / reps * 1e6
     print(f"  {'reset_random_where of the 1 % reset through Python (wall clock)':62s} {t:10.1f} {'':>20s} {N / t:9.3f} {t / d2d:7.2f}", flush=True)
     bad = int(data.nonfinite_mask().sum())
     print(f"#   (after the resets {bad} of {N} environments are non-finite)")
