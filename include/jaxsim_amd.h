@@ -407,6 +407,75 @@ int jxs_action_destroy(jxs_action* action);
 int jxs_env_act(jxs_model* model, const jxs_action* action, const void* state, const void* actions, int act_dtype,
                 int64_t act_ld, const void* feed_forward, void* out_tau, int N, void* stream);
 
+/* jxs_env_evaluate: the reward and the termination flags of a policy step, one launch that writes per environment e < N
+ *   `reward[e]` (one word of `reward_dtype`, contiguous) and `done[e]` (one byte: bit 0 JXS_DONE_TERMINATED, bit 1
+ *   JXS_DONE_TRUNCATED -- directly the `mask` of jxs_env_select and jxs_env_randomize), and optionally `fired[e]` (uint32,
+ *   bit c: condition c fired), `terms` = [N][terms_ld] (the K per-term contributions, environment-major, of `terms_dtype`)
+ *   and the in/out episode counter `steps[e]` (int32) -- what the reference's user writes as a reward function and a done
+ *   predicate over `data.base_position`, `data.joint_positions`, `data.base_velocity` ... under vmap.  With it
+ *   act -> step x k -> evaluate -> jxs_env_randomize(done) -> observe needs no host trip.
+ *   The law is described once per model by an immutable table (jxs_evaluation_desc).  It has D slots (1 <= D <=
+ *   JXS_EVAL_MAX_SLOTS), each {kind, source, index} with `offset[d]` and `scale[d]` exactly as a slot of jxs_env_observe
+ *   (NULL: zeros / ones), and each optionally with a target {source, row} in `targets` [D][2] (source -1, or NULL
+ *   `targets`: none), the commanded value of the environment, read from a source block.  Every operation is rounded on its
+ *   own in the model's dtype:
+ *     x_d = target ? raw_d - source[row][e] : raw_d
+ *     y_d = (x_d - offset[d]) * scale[d]
+ *   Every slot belongs to exactly one term or one condition.  Term t (0 <= K <= JXS_EVAL_MAX_TERMS), `terms` [K][4] =
+ *   {first, count, inner, outer} and `term_params` [K][3] = {weight, lo, hi}, owns the slots first .. first + count - 1:
+ *     v_d = JXS_EVAL_IDENTITY y_d | JXS_EVAL_ABS |y_d| | JXS_EVAL_SQUARE y_d * y_d | JXS_EVAL_EXCESS max(|y_d| - 1, 0)
+ *     s_t = v_first, then s_t = s_t + v_d in slot order
+ *     o_t = JXS_EVAL_OUTER_IDENTITY s_t | JXS_EVAL_OUTER_EXP exp(-s_t)       (the accurate exponential of the dtype)
+ *     p_t = clamp(weight * o_t, lo, hi)       (clamp(x, lo, hi) = x < lo ? lo : (hi < x ? hi : x): a NaN stays a NaN)
+ *   (JXS_EVAL_EXCESS with offset = the centre and scale = 1 / half-width of a window measures how far a value lies outside
+ *   it, in half-widths: joint limits.)  Then r = p_0, r = r + p_t in term order (K = 0: r = 0), r = clamp(r, reward_lo,
+ *   reward_hi).  Condition c (0 <= C <= JXS_EVAL_MAX_CONDITIONS), `conditions` [C][2] = {slot, kind} and
+ *   `condition_limits` [C][2] = {lo, hi}, fires when !(lo <= y && y <= hi) -- a NaN fires; either limit may be infinite --
+ *   and sets the bit of its kind (JXS_EVAL_TERMINATED, JXS_EVAL_TRUNCATED) in `done` and bit c in `fired`.  With `steps`
+ *   non-NULL (then max_steps > 0): n = steps[e] + 1; n >= max_steps sets JXS_DONE_TRUNCATED (and no bit of `fired`);
+ *   steps[e] = done ? 0 : n -- an environment flagged done starts its next episode at zero, since the caller resets it
+ *   with that same mask.  Last, bit 0 of done adds `termination_reward` to r.
+ *   jxs_evaluation_create refuses with JXS_EINVAL: D, K or C outside their ranges, an unknown kind, inner, outer or
+ *   condition kind, a row, component, source or target out of range (`source_rows` as for jxs_observation_create), an
+ *   empty term, overlapping slot ranges, a slot of no term and no condition or of two, an offset, scale, weight or
+ *   termination_reward that is not finite in the model's dtype, lo > hi or a NaN limit (infinities allowed).  A table may
+ *   be used with every model of the same state layout and dtype.
+ *   jxs_env_evaluate writes reward[0 .. N), done[0 .. N), fired[0 .. N), steps[0 .. N) and columns < K of rows < N of
+ *   `terms`, each only when its pointer is non-NULL, and nothing else; at least one of `reward` and `done` is non-NULL.
+ *   `reward_dtype` and `terms_dtype` are JXS_F32 or the model's dtype.  Padding columns of the last tile are never read
+ *   and no source is read beyond its storage.  Asynchronous on `stream`; no allocation, synchronisation, memset or host
+ *   read (legal between two jxs_step launches and inside a stream capture).  JXS_EINVAL: a null model, table or state,
+ *   NULL reward and done, N <= 0, terms_ld < K, an unknown representation or dtype, `steps` with max_steps <= 0, a used
+ *   source whose pointer is NULL, a table of another layout or dtype, a misaligned block.                             */
+#define JXS_EVAL_MAX_SLOTS 1024
+#define JXS_EVAL_MAX_TERMS 32
+#define JXS_EVAL_MAX_CONDITIONS 32
+#define JXS_DONE_TERMINATED 1
+#define JXS_DONE_TRUNCATED 2
+enum { JXS_EVAL_IDENTITY = 0, JXS_EVAL_ABS = 1, JXS_EVAL_SQUARE = 2, JXS_EVAL_EXCESS = 3 };
+enum { JXS_EVAL_OUTER_IDENTITY = 0, JXS_EVAL_OUTER_EXP = 1 };
+enum { JXS_EVAL_TERMINATED = 0, JXS_EVAL_TRUNCATED = 1 };
+typedef struct jxs_evaluation_desc {
+  int32_t D, K, C;
+  const int32_t* slots;           /* [D][3] = kind, source, index (JXS_OBS_*) */
+  const int32_t* targets;         /* [D][2] = source, row; source -1: none; may be NULL */
+  const double* offset;           /* [D], may be NULL */
+  const double* scale;            /* [D], may be NULL */
+  const int32_t* terms;           /* [K][4] = first, count, inner, outer */
+  const double* term_params;      /* [K][3] = weight, lo, hi */
+  const int32_t* conditions;      /* [C][2] = slot, kind */
+  const double* condition_limits; /* [C][2] = lo, hi */
+  double reward_lo, reward_hi, termination_reward;
+  int32_t source_rows[4];
+} jxs_evaluation_desc;
+typedef struct jxs_evaluation jxs_evaluation;
+int jxs_evaluation_create(jxs_model* model, const jxs_evaluation_desc* desc, jxs_evaluation** out);
+int jxs_evaluation_destroy(jxs_evaluation* evaluation);
+int jxs_env_evaluate(jxs_model* model, const jxs_evaluation* evaluation, const void* state,
+                     const void* const sources[4], int N, int velocity_representation, void* reward, int reward_dtype,
+                     uint8_t* done, uint32_t* fired, void* terms, int terms_dtype, int64_t terms_ld, int32_t* steps,
+                     int max_steps, void* stream);
+
 /* RigidContacts only.  A contact-force QP or an impact solve whose result is not finite (fp32 on a numerically
  * singular stance) is DISCARDED -- that environment takes the step without contact forces / without the
  * velocity reset instead of poisoning its state -- where the reference would propagate NaN

@@ -88,6 +88,28 @@ class Layout(C.Structure):
         "row_vang", "row_sd", "row_m", "group", "tile", "dtype", "row_mode")]  # fmt: skip
 
 
+class EvaluationDesc(C.Structure):
+    """``jxs_evaluation_desc`` (include/jaxsim_amd.h)."""
+
+    _fields_ = [
+        ("D", C.c_int32),
+        ("K", C.c_int32),
+        ("C", C.c_int32),
+        ("slots", C.POINTER(C.c_int32)),
+        ("targets", C.POINTER(C.c_int32)),
+        ("offset", C.POINTER(C.c_double)),
+        ("scale", C.POINTER(C.c_double)),
+        ("terms", C.POINTER(C.c_int32)),
+        ("term_params", C.POINTER(C.c_double)),
+        ("conditions", C.POINTER(C.c_int32)),
+        ("condition_limits", C.POINTER(C.c_double)),
+        ("reward_lo", C.c_double),
+        ("reward_hi", C.c_double),
+        ("termination_reward", C.c_double),
+        ("source_rows", C.c_int32 * 4),
+    ]
+
+
 def dtype_code(dtype) -> int:
     dt = np.dtype(dtype)
     if dt == np.float32:
@@ -249,6 +271,9 @@ def _declare(lib):
         "jxs_action_create": [vp, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(vp)],
         "jxs_action_destroy": [vp],
         "jxs_env_act": [vp, vp, vp, vp, C.c_int, C.c_int64, vp, vp, C.c_int, vp],
+        "jxs_evaluation_create": [vp, C.POINTER(EvaluationDesc), C.POINTER(vp)],
+        "jxs_evaluation_destroy": [vp],
+        "jxs_env_evaluate": [vp, vp, vp, C.POINTER(vp), C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, C.c_int, C.c_int64, vp, C.c_int, vp],
         "jxs_step_repeat": [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp],
         "jxs_step_repeat_timed": [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, C.POINTER(C.c_double)],
         "jxs_refresh_kinematics": [vp, vp, vp, vp, C.c_int, vp],

@@ -24,6 +24,7 @@
 
 #include "../../include/jaxsim_amd.h"
 #include "jxs_env_act.h"
+#include "jxs_env_evaluate.h"
 #include "jxs_env_observe.h"
 #include "jxs_env_ops.h"
 #include "jxs_env_random.h"
@@ -54,7 +55,10 @@ namespace {
 std::atomic<int> g_knobs{-1}, g_duo_max_blocks{0};
 std::atomic<int> g_observe_envs_per_wave{0};  // JXS_OBSERVE_ENVS_PER_WAVE: 0 = the launcher's own rule (tools/bench_env_observe.py)
 std::atomic<int> g_act_envs_per_wave{0};  // JXS_ACT_ENVS_PER_WAVE: 0 = the launcher's own rule (tools/bench_env_act.py)
+std::atomic<int> g_evaluate_envs_per_wave{0};  // JXS_EVALUATE_ENVS_PER_WAVE: 0 = the launcher's own rule (tools/bench_env_evaluate.py)
 void load_knobs() {
+  const char* ew = std::getenv("JXS_EVALUATE_ENVS_PER_WAVE");
+  g_evaluate_envs_per_wave.store(ew == nullptr ? 0 : std::atoi(ew));
   const char* ow = std::getenv("JXS_OBSERVE_ENVS_PER_WAVE");
   g_observe_envs_per_wave.store(ow == nullptr ? 0 : std::atoi(ow));
   const char* aw = std::getenv("JXS_ACT_ENVS_PER_WAVE");
@@ -191,6 +195,20 @@ struct jxs_action {
   bool reads_actions = false;  // some joint has a column
   void* table = nullptr;       // device
   size_t params_at = 0;        // bytes from `table`
+};
+
+// an immutable reward and termination table on the device (jxs_evaluation_create), in one allocation: per slot its packed
+// word (jxs_obs::pack_slot), target word (jxs_eval::pack_target), offset and scale; per term {first, count, inner, outer} and
+// {weight, lo, hi}; per condition {slot, kind} and {lo, hi}
+struct jxs_evaluation {
+  int dtype = JXS_F32;
+  int D = 0, K = 0, C = 0, n_rows = 0, n_joints = 0;
+  int32_t source_rows[jxs_obs::kSources] = {0, 0, 0, 0};
+  unsigned sources_used = 0;             // bit s: some slot or target reads source s
+  unsigned derived_used[3] = {0, 0, 0};  // per JXS_REPR_*: the derived values a launch computes (jxs_obs::derived_used)
+  double reward_lo = 0, reward_hi = 0, termination_reward = 0;
+  void* table = nullptr;  // device
+  size_t targets_at = 0, offset_at = 0, scale_at = 0, terms_at = 0, term_params_at = 0, conds_at = 0, cond_limits_at = 0;  // bytes from `table`
 };
 
 struct jxs_model {
@@ -719,6 +737,37 @@ struct ObsSources {
   int rows[jxs_obs::kSources];
 };
 
+// Steps 1 and 2 of jxs_env_observe_kernel and of jxs_env_evaluate_kernel: the derived values `used` names, of the wave's
+// n_env environments, into its LDS slice derived[kDerived][E].  word_at(rows, row, e) is the word of a row of environment e
+// of the wave in a tiled block of `rows` rows.  Ends behind the wave's barrier: every lane may read every value.
+template <typename T, typename WordAt>
+__device__ __forceinline__ void env_derived_values(const T* __restrict__ state, const jxs_obs::Shape& sh, unsigned used, int lane, int env_shift,
+                                                   int n_env, T* derived, WordAt word_at) {
+  const int E = 1 << env_shift;
+  for (int i = lane; i < (jxs_obs::kDerivedRot << env_shift); i += 64) {
+    const int e = i & (E - 1), k = i >> env_shift;
+    if (((used >> k) & 1u) && e < n_env) {
+      T q[4];
+      for (int j = 0; j < 4; ++j) q[j] = state[word_at(sh.n_rows, jxs_obs::row_quat(sh) + j, e)];
+      derived[i] = jxs_obs::unit_quaternion_component(q, k);
+    }
+  }
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  for (int i = (jxs_obs::kDerivedRot << env_shift) + lane; i < (jxs_obs::kDerived << env_shift); i += 64) {
+    const int e = i & (E - 1), d = i >> env_shift;
+    if (((used >> d) & 1u) && e < n_env) {
+      T u[4];
+      for (int j = 0; j < 4; ++j) u[j] = (used & 1u) ? derived[(j << env_shift) + e] : T(0);
+      derived[i] = jxs_obs::derived_from_unit<T>(sh, d, u, [&](int r) { return state[word_at(sh.n_rows, r, e)]; });
+    }
+  }
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
 template <typename T, typename O>
 __global__ void __launch_bounds__(256) jxs_env_observe_kernel(const T* __restrict__ state, ObsSources src, const int32_t* __restrict__ codes,
                                                               const T* __restrict__ offset, const T* __restrict__ scale, int D, unsigned used,
@@ -741,30 +790,7 @@ __global__ void __launch_bounds__(256) jxs_env_observe_kernel(const T* __restric
   int32_t code = 0;
   T off = T(0), sc = T(1);
   if (lane < D) code = codes[lane], off = offset[lane], sc = scale[lane];
-  if (used != 0) {
-    for (int i = lane; i < (jxs_obs::kDerivedRot << env_shift); i += 64) {
-      const int e = i & (E - 1), k = i >> env_shift;
-      if (((used >> k) & 1u) && e < n_env) {
-        T q[4];
-        for (int j = 0; j < 4; ++j) q[j] = state[word_at(sh.n_rows, jxs_obs::row_quat(sh) + j, e)];
-        derived[i] = jxs_obs::unit_quaternion_component(q, k);
-      }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    for (int i = (jxs_obs::kDerivedRot << env_shift) + lane; i < (jxs_obs::kDerived << env_shift); i += 64) {
-      const int e = i & (E - 1), d = i >> env_shift;
-      if (((used >> d) & 1u) && e < n_env) {
-        T u[4];
-        for (int j = 0; j < 4; ++j) u[j] = (used & 1u) ? derived[(j << env_shift) + e] : T(0);
-        derived[i] = jxs_obs::derived_from_unit<T>(sh, d, u, [&](int r) { return state[word_at(sh.n_rows, r, e)]; });
-      }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  }
+  if (used != 0) env_derived_values(state, sh, used, lane, env_shift, n_env, derived, word_at);
   O* const orow = out + (size_t)env0 * (size_t)out_ld;
   for (int c = lane; c < D; c += 64) {
     if (c != lane) code = codes[c], off = offset[c], sc = scale[c];
@@ -777,6 +803,104 @@ __global__ void __launch_bounds__(256) jxs_env_observe_kernel(const T* __restric
       const T x = from_row ? base[word_at(rows, index, e)] : derived[(index << env_shift) + e];  // (one load per lane, by its kind)
       orow[(size_t)e * (size_t)out_ld + c] = (O)jxs_obs::affine(x, off, sc);
     }
+  }
+}
+
+// The reward, the done byte and their optional companions of every environment (the law is jxs_env_evaluate.h: every output
+// is what jxs_eval::evaluate_env gives for its environment).  The frame of jxs_env_observe_kernel: a wave takes E =
+// 2^env_shift consecutive environments -- whole tiles, E >= T --, and the waves of a workgroup (4, or 2 or 1 where the LDS
+// of 4 would pass 64 KB) share nothing.  A wave's LDS slice is [kDerived + K + C][E] words:
+//   1., 2. the derived values the table's slots read (env_derived_values, as in the observation), skipped without such slots;
+//   3. work items i = lane, lane + 64, ... over (K + C) x E, environment fastest, so that the lanes of one term read
+//      neighbouring columns of a tile.  A term item walks its slots in order -- the slot words are uniform across the lanes
+//      of a term, x comes from global memory or from the derived slice --, accumulates, applies outer, weight and clamp, and
+//      stores p into LDS [K][E] (and into `terms`); a condition item stores whether it fired into LDS [C][E];
+//   4. lane e < n_env sums the p of its environment in term order, ORs the bits, applies the counter rule and stores
+//      reward, done, fired and steps: the stores of the lanes are contiguous.
+// Only environments below N are touched: padding columns of the last tile are never read, a source is read at rows below
+// its own count only (the host checked every slot and target).  The steps of one wave follow each other in program order and
+// LDS serves a wave's accesses in order; the fences keep the compiler from moving them.
+template <typename T>
+struct EvalTable {
+  const int32_t* codes;     // [D]
+  const int32_t* targets;   // [D]
+  const T* offset;          // [D]
+  const T* scale;           // [D]
+  const int32_t* terms;     // [K][4]
+  const T* term_params;     // [K][3]
+  const int32_t* conds;     // [C][2]
+  const T* cond_limits;     // [C][2]
+  int K, C;
+  T reward_lo, reward_hi, termination_reward;
+};
+
+template <typename T, typename R, typename TT>
+__global__ void __launch_bounds__(256) jxs_env_evaluate_kernel(const T* __restrict__ state, ObsSources src, EvalTable<T> tb, unsigned used,
+                                                               jxs_obs::Shape sh, int N, int tile_shift, int env_shift, R* __restrict__ reward,
+                                                               uint8_t* __restrict__ done, uint32_t* __restrict__ fired, TT* __restrict__ terms,
+                                                               long long terms_ld, int32_t* __restrict__ steps, int max_steps) {
+  extern __shared__ __align__(16) unsigned char jxs_evaluate_lds[];
+  const int lane = threadIdx.x & 63;
+  const int E = 1 << env_shift, tmask = (1 << tile_shift) - 1;
+  const int K = tb.K, C = tb.C;
+  const long long env0 = ((long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) << env_shift;
+  if (env0 >= N) return;  // (wave-uniform)
+  const int n_env = (long long)N - env0 < E ? (int)(N - env0) : E;
+  T* derived = reinterpret_cast<T*>(jxs_evaluate_lds) + (size_t)(threadIdx.x >> 6) * (size_t)((jxs_obs::kDerived + K + C) << env_shift);
+  T* const contrib = derived + (jxs_obs::kDerived << env_shift);                          // [K][E]
+  uint32_t* const fire = reinterpret_cast<uint32_t*>(contrib + ((size_t)K << env_shift));  // [C][E], one word of T each
+  // word of row `row` of environment env0 + e in a tiled block of `rows` rows (rows * T < 2^30: the host checks)
+  auto word_at = [&](int rows, int row, int e) {
+    const long long env = env0 + e;
+    return (size_t)(env >> tile_shift) * (size_t)(rows << tile_shift) + (size_t)((row << tile_shift) + (int)(env & tmask));
+  };
+  auto source = [&](int s) { return static_cast<const T*>(s == 0 ? src.ptr[0] : s == 1 ? src.ptr[1] : s == 2 ? src.ptr[2] : src.ptr[3]); };
+  auto source_rows = [&](int s) { return s == 0 ? src.rows[0] : s == 1 ? src.rows[1] : s == 2 ? src.rows[2] : src.rows[3]; };
+  if (used != 0) env_derived_values(state, sh, used, lane, env_shift, n_env, derived, word_at);
+  const bool want_terms = reward != nullptr || terms != nullptr;  // (without either nobody reads a contribution)
+  for (int i = lane; i < ((K + C) << env_shift); i += 64) {
+    const int e = i & (E - 1), item = i >> env_shift;
+    if (e >= n_env || (item < K && !want_terms)) continue;
+    // (A term item walks its slots one at a time.  Asking for the loads of eight slots at once, unconditionally, measured
+    // slower, not faster -- profiles/env_evaluate_chunked_loads.txt against profiles/env_evaluate.txt --: the walk is bound by
+    // the cache lines its accesses touch, not by their latency)
+    auto y = [&](int d) {
+      const int32_t code = tb.codes[d], tg = tb.targets[d];
+      const int kind = jxs_obs::packed_kind(code), index = jxs_obs::packed_index(code), s = jxs_obs::packed_source(code);
+      T raw;
+      if (kind == jxs_obs::kStateRow) raw = state[word_at(sh.n_rows, index, e)];
+      else if (kind == jxs_obs::kSourceRow) raw = source(s)[word_at(source_rows(s), index, e)];
+      else raw = derived[(index << env_shift) + e];
+      T target = T(0);
+      if (tg >= 0) target = source(jxs_eval::target_source(tg))[word_at(source_rows(jxs_eval::target_source(tg)), jxs_eval::target_row(tg), e)];
+      return jxs_obs::affine(jxs_eval::slot_x(raw, tg >= 0, target), tb.offset[d], tb.scale[d]);
+    };
+    if (item < K) {
+      const int32_t* info = tb.terms + 4 * item;
+      const T* w = tb.term_params + 3 * item;
+      const T p = jxs_eval::term_value<T>(info[0], info[1], info[2], info[3], w[0], w[1], w[2], y);
+      contrib[i] = p;
+      if (terms != nullptr) terms[(size_t)(env0 + e) * (size_t)terms_ld + item] = (TT)p;
+    } else {
+      const int c = item - K;
+      fire[(c << env_shift) + e] = jxs_eval::fires(y(tb.conds[2 * c]), tb.cond_limits[2 * c], tb.cond_limits[2 * c + 1]) ? 1u : 0u;
+    }
+  }
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  if (lane < n_env) {
+    const size_t env = (size_t)env0 + lane;
+    unsigned dn = 0, fr = 0;
+    for (int c = 0; c < C; ++c)
+      if (fire[(c << env_shift) + lane] != 0) fr |= 1u << c, dn |= 1u << tb.conds[2 * c + 1];
+    if (steps != nullptr) steps[env] = jxs_eval::counted(steps[env], max_steps, &dn);
+    if (reward != nullptr) {
+      const T r = jxs_eval::total<T>(K, tb.reward_lo, tb.reward_hi, [&](int t) { return contrib[(t << env_shift) + lane]; });
+      reward[env] = (R)jxs_eval::terminal(r, dn, tb.termination_reward);
+    }
+    if (done != nullptr) done[env] = (uint8_t)dn;
+    if (fired != nullptr) fired[env] = fr;
   }
 }
 
@@ -1331,6 +1455,151 @@ int jxs_env_observe(jxs_model* model, const jxs_observation* observation, const 
       using O = decltype(o);
       hipLaunchKernelGGL((jxs_env_observe_kernel<T, O>), env_grid(env_waves(N, env_shift)), dim3(kEnvBlock), lds, s, static_cast<const T*>(state),
                          src, codes, off, sc, ob.D, used, sh, N, t.tile_shift, env_shift, static_cast<O*>(out), (long long)out_ld);
+    });
+    return launched(who);
+  });
+}
+
+int jxs_evaluation_create(jxs_model* model, const jxs_evaluation_desc* desc, jxs_evaluation** out) {
+  if (out == nullptr) return fail(JXS_EINVAL, "null out");
+  *out = nullptr;
+  if (model == nullptr) return fail(JXS_EINVAL, "null model");
+  if (desc == nullptr) return fail(JXS_EINVAL, "null desc");
+  const char* const who = "jxs_evaluation_create";
+  return with_typed(model, [&](auto* mt) -> int {
+    using T = typename std::remove_pointer_t<decltype(mt)>::value_type;
+    const auto& P = mt->pk.P;
+    const jxs_eval::Desc d{desc->D, desc->K, desc->C, desc->slots, desc->targets, desc->offset, desc->scale, desc->terms, desc->term_params,
+                           desc->conditions, desc->condition_limits, desc->reward_lo, desc->reward_hi, desc->termination_reward};
+    int bad = -1, slot_code = jxs_obs::kOk;
+    const int err = jxs_eval::table_error(d, P.n_rows, desc->source_rows, T(0), &bad, &slot_code);
+    if (err == jxs_eval::kBadWidth)
+      return refuse(who, "D = " + std::to_string(desc->D) + ", K = " + std::to_string(desc->K) + ", C = " + std::to_string(desc->C) + " outside [1, " +
+                             std::to_string(JXS_EVAL_MAX_SLOTS) + "], [0, " + std::to_string(JXS_EVAL_MAX_TERMS) + "], [0, " +
+                             std::to_string(JXS_EVAL_MAX_CONDITIONS) + "], or a null table");
+    if (err != jxs_eval::kOk) {
+      const std::string at = std::to_string(bad);
+      switch (err) {
+        case jxs_eval::kBadSlot:
+          return refuse(who, "slot " + at + ": " + (slot_code == jxs_obs::kBadKind ? "unknown kind" : slot_code == jxs_obs::kBadSource ? "source out of range or without rows" : "row or component out of range"));
+        case jxs_eval::kBadTarget: return refuse(who, "slot " + at + ": target source or row out of range");
+        case jxs_eval::kBadTerm: return refuse(who, "term " + at + ": unknown inner or outer");
+        case jxs_eval::kBadRange: return refuse(who, "term " + at + ": an empty slot range, one outside the table or one that overlaps an earlier term's");
+        case jxs_eval::kBadCondition: return refuse(who, "condition " + at + ": unknown kind, or a slot outside the table or owned already");
+        case jxs_eval::kUnowned: return refuse(who, "slot " + at + " belongs to no term and no condition");
+        case jxs_eval::kNotFinite:
+          return refuse(who, (bad < 0 ? std::string("termination_reward") : "entry " + at + ": offset, scale or weight") + " not finite in the model's dtype");
+        default: return refuse(who, (bad < 0 ? std::string("the reward limits") : "the limits of entry " + at) + ": lo above hi, NaN or not finite in the model's dtype");
+      }
+    }
+    auto ev = std::make_unique<jxs_evaluation>();
+    const int D = desc->D, K = desc->K, C = desc->C;
+    ev->dtype = model->dtype, ev->D = D, ev->K = K, ev->C = C, ev->n_rows = P.n_rows, ev->n_joints = P.n;
+    ev->reward_lo = desc->reward_lo, ev->reward_hi = desc->reward_hi, ev->termination_reward = desc->termination_reward;
+    for (int s = 0; s < jxs_obs::kSources; ++s) {
+      ev->source_rows[s] = desc->source_rows[s] > 0 ? desc->source_rows[s] : 0;
+      if (ev->source_rows[s] >= (1 << 26)) return refuse(who, "a source of 2^26 rows or more");
+    }
+    if (P.n_rows >= (1 << 26)) return refuse(who, "a state of 2^26 rows or more");
+    size_t at = 0;
+    auto place = [&](size_t bytes) {
+      const size_t here = at;
+      at += (bytes + 15) / 16 * 16;
+      return here;
+    };
+    place((size_t)D * sizeof(int32_t));
+    ev->targets_at = place((size_t)D * sizeof(int32_t));
+    ev->offset_at = place((size_t)D * sizeof(T));
+    ev->scale_at = place((size_t)D * sizeof(T));
+    ev->terms_at = place((size_t)K * 4 * sizeof(int32_t));
+    ev->term_params_at = place((size_t)K * 3 * sizeof(T));
+    ev->conds_at = place((size_t)C * 2 * sizeof(int32_t));
+    ev->cond_limits_at = place((size_t)C * 2 * sizeof(T));
+    std::vector<unsigned char> host(at + 16, 0);
+    int32_t* codes = reinterpret_cast<int32_t*>(host.data());
+    int32_t* targets = reinterpret_cast<int32_t*>(host.data() + ev->targets_at);
+    T* off = reinterpret_cast<T*>(host.data() + ev->offset_at);
+    T* sc = reinterpret_cast<T*>(host.data() + ev->scale_at);
+    for (int i = 0; i < D; ++i) {
+      const jxs_obs::Slot s{d.slots[3 * i], d.slots[3 * i + 1], d.slots[3 * i + 2]};
+      const int ts = d.targets != nullptr ? d.targets[2 * i] : -1;
+      codes[i] = jxs_obs::pack_slot(s), targets[i] = jxs_eval::pack_target(ts, ts < 0 ? 0 : d.targets[2 * i + 1]);
+      off[i] = static_cast<T>(d.offset != nullptr ? d.offset[i] : 0.0), sc[i] = static_cast<T>(d.scale != nullptr ? d.scale[i] : 1.0);
+      if (s.kind == jxs_obs::kSourceRow) ev->sources_used |= 1u << s.source;
+      if (ts >= 0) ev->sources_used |= 1u << ts;
+    }
+    int32_t* terms = reinterpret_cast<int32_t*>(host.data() + ev->terms_at);
+    T* tp = reinterpret_cast<T*>(host.data() + ev->term_params_at);
+    for (int i = 0; i < 4 * K; ++i) terms[i] = d.terms[i];
+    for (int i = 0; i < 3 * K; ++i) tp[i] = static_cast<T>(d.term_params[i]);
+    int32_t* conds = reinterpret_cast<int32_t*>(host.data() + ev->conds_at);
+    T* cl = reinterpret_cast<T*>(host.data() + ev->cond_limits_at);
+    for (int i = 0; i < 2 * C; ++i) conds[i] = d.conds[i], cl[i] = static_cast<T>(d.cond_limits[i]);
+    for (int r = 0; r < 3; ++r) ev->derived_used[r] = jxs_obs::derived_used(d.slots, D, r);
+    if ((ev->table = upload_table(host, "uploading the evaluation table")) == nullptr) return JXS_ENODEVICE;
+    *out = ev.release();
+    return JXS_OK;
+  });
+}
+int jxs_evaluation_destroy(jxs_evaluation* evaluation) { return destroy_table(evaluation); }
+
+int jxs_env_evaluate(jxs_model* model, const jxs_evaluation* evaluation, const void* state, const void* const sources[4], int N,
+                     int velocity_representation, void* reward, int reward_dtype, uint8_t* done, uint32_t* fired, void* terms, int terms_dtype,
+                     int64_t terms_ld, int32_t* steps, int max_steps, void* stream) {
+  const char* const who = "jxs_env_evaluate";
+  if (model == nullptr || evaluation == nullptr || state == nullptr) return refuse(who, "null argument");
+  if (reward == nullptr && done == nullptr) return refuse(who, "null reward and done: at least one of them is needed");
+  if (N <= 0) return refuse(who, "N must be positive");
+  if (!repr_ok(velocity_representation)) return refuse(who, "unknown velocity representation");
+  if (reward != nullptr && reward_dtype != JXS_F32 && reward_dtype != model->dtype) return refuse(who, "reward_dtype must be JXS_F32 or the model's dtype");
+  if (terms != nullptr && terms_dtype != JXS_F32 && terms_dtype != model->dtype) return refuse(who, "terms_dtype must be JXS_F32 or the model's dtype");
+  const jxs_evaluation& ev = *evaluation;
+  if (terms != nullptr && terms_ld < ev.K) return refuse(who, "terms_ld = " + std::to_string(terms_ld) + " below K = " + std::to_string(ev.K));
+  if (steps != nullptr && max_steps <= 0) return refuse(who, "steps is given, and max_steps = " + std::to_string(max_steps) + " is not positive");
+  ObsSources src{};
+  for (int s = 0; s < jxs_obs::kSources; ++s) {
+    if (!((ev.sources_used >> s) & 1u)) continue;  // (a pointer the table does not use is not looked at)
+    if (sources == nullptr || sources[s] == nullptr) return refuse(who, "the table reads source " + std::to_string(s) + ", whose pointer is null");
+    src.ptr[s] = sources[s], src.rows[s] = ev.source_rows[s];
+  }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  return with_typed(model, [&](auto* mt) {
+    using T = typename std::remove_pointer_t<decltype(mt)>::value_type;
+    const auto& P = mt->pk.P;
+    if (!table_fits(ev, model->dtype, P)) return refuse(who, "the evaluation table was created for another state layout or dtype");
+    int max_rows = P.n_rows;
+    for (int k = 0; k < jxs_obs::kSources; ++k) max_rows = std::max(max_rows, src.rows[k]);
+    EnvTile t;
+    if (const int rc = env_tile(who, mt->pk.G, max_rows, t)) return rc;
+    const bool own_reward = reward == nullptr || reward_dtype == model->dtype, own_terms = terms == nullptr || terms_dtype == model->dtype;
+    bool aligned = (uintptr_t)state % sizeof(T) == 0 && (uintptr_t)reward % (own_reward ? sizeof(T) : 4) == 0 &&
+                   (uintptr_t)terms % (own_terms ? sizeof(T) : 4) == 0 && (uintptr_t)fired % 4 == 0 && (uintptr_t)steps % 4 == 0;
+    for (int k = 0; k < jxs_obs::kSources; ++k) aligned = aligned && (uintptr_t)src.ptr[k] % sizeof(T) == 0;
+    if (!aligned) return refuse(who, "state, sources, reward, terms, fired and steps must be aligned to their element type");
+    const int env_shift = jxs_env::env_shift_for(N, t.tile_shift, knob(g_evaluate_envs_per_wave));
+    // (kDerived + K + C) E words per wave: as many waves per workgroup, out of 4, 2, 1, as fit 64 KB (the worst case, 86 records
+    // of 64 fp64 environments, is 44 KB for one wave)
+    const size_t per_wave = (size_t)((jxs_obs::kDerived + ev.K + ev.C) << env_shift) * sizeof(T);
+    int waves_per_block = 4;
+    while (waves_per_block > 1 && waves_per_block * per_wave > 64 * 1024) waves_per_block >>= 1;
+    const unsigned used = ev.derived_used[velocity_representation];
+    const jxs_obs::Shape sh{P.n_rows, P.n, velocity_representation};
+    const unsigned char* b = static_cast<const unsigned char*>(ev.table);
+    const EvalTable<T> tb{reinterpret_cast<const int32_t*>(b), reinterpret_cast<const int32_t*>(b + ev.targets_at), reinterpret_cast<const T*>(b + ev.offset_at),
+                          reinterpret_cast<const T*>(b + ev.scale_at), reinterpret_cast<const int32_t*>(b + ev.terms_at),
+                          reinterpret_cast<const T*>(b + ev.term_params_at), reinterpret_cast<const int32_t*>(b + ev.conds_at),
+                          reinterpret_cast<const T*>(b + ev.cond_limits_at), ev.K, ev.C, static_cast<T>(ev.reward_lo), static_cast<T>(ev.reward_hi),
+                          static_cast<T>(ev.termination_reward)};
+    // (env_grid counts four waves per workgroup: a workgroup of 4 / f waves needs f times as many)
+    const dim3 grid = env_grid(env_waves(N, env_shift) * (4 / waves_per_block));
+    with_io_type<T>(own_reward, [&](auto r) {
+      using R = decltype(r);
+      with_io_type<T>(own_terms, [&](auto w) {
+        using TT = decltype(w);
+        hipLaunchKernelGGL((jxs_env_evaluate_kernel<T, R, TT>), grid, dim3(64 * waves_per_block), waves_per_block * per_wave, s,
+                           static_cast<const T*>(state), src, tb, used, sh, N, t.tile_shift, env_shift, static_cast<R*>(reward), done, fired,
+                           static_cast<TT*>(terms), (long long)terms_ld, steps, max_steps);
+      });
     });
     return launched(who);
   });

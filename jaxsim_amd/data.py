@@ -642,6 +642,90 @@ class JaxSimModelData:
         del keep
         return out
 
+    def evaluate(self, spec: "RewardSpec", *, sources: dict | None = None, reward=None, done=None, terms=None, fired=None, steps=None,
+                 max_steps: int = 0):  # fmt: skip
+        """``(reward, done)`` of a policy step, computed by one kernel (``jxs_env_evaluate``) on the current stream -- the reward
+        function and the done predicate that the reference's user writes over ``data.base_position``, ``data.joint_positions``,
+        ``data.base_velocity`` ... under ``vmap``: no download, no synchronisation.  ``done`` holds one byte per environment, bit 0
+        ``DONE_TERMINATED``, bit 1 ``DONE_TRUNCATED``, and goes into ``reset_where`` / ``reset_random_where`` as it is.
+
+        ``sources``: as for ``observe``, ``{name: DeviceArray}`` for every source the spec names (also as a target).
+        ``reward=None`` returns a new ``runtime.DeviceMatrix`` ``(batch_size, 1)`` of this object's dtype; a ``DeviceMatrix`` of
+        that shape or an object with a ``__cuda_array_interface__`` of shape ``(batch_size,)`` or ``(batch_size, 1)``, contiguous,
+        float32 or this object's dtype, is written in place.  ``done=None`` returns a new ``runtime.DeviceMask``; a ``DeviceMask``
+        or a ``__cuda_array_interface__`` of ``batch_size`` bytes (``|u1`` / ``|b1``) is written in place.  Optional outputs,
+        written only when given: ``fired``, a ``runtime.DeviceWords`` or ``<u4`` device vector (bit ``c``: condition
+        ``spec.condition_names[c]`` fired); ``terms``, a ``DeviceMatrix`` or 2-D ``__cuda_array_interface__`` ``(batch_size,
+        spec.n_terms)`` with a row stride, float32 or this object's dtype (column ``t``: the contribution of
+        ``spec.term_names[t]``).  ``steps``: the episode counters, a ``runtime.DeviceIndices`` or ``<i4`` device vector, updated in
+        place with ``max_steps > 0``: an environment whose counter reaches ``max_steps`` is truncated, and the counter of every
+        environment flagged done restarts at zero.  ``ValueError`` before any launch for a spec of another layout or dtype, a
+        missing, unknown or mis-shaped source, a wrong output, ``steps`` without a positive ``max_steps``."""
+        from .api.model import _device_model_fast
+
+        self._check_spec(spec, RewardSpec, "spec")
+        st = self._state
+        sources = dict(sources or {})
+        unknown = sorted(set(sources) - set(spec.source_names))
+        if unknown:
+            raise ValueError(f"sources {unknown} are not named by the spec (it names {list(spec.source_names)})")
+        blocks = []
+        for name, rows in zip(spec.source_names, spec.source_rows):
+            blk = sources.get(name)
+            if blk is None:
+                raise ValueError(f"the spec reads the source {name!r}, which was not given")
+            self._check_block(f"source {name!r}", blk, rows)
+            blocks.append(blk)
+        N, K, dt = st.cols, spec.n_terms, self.dtype
+        floats = tuple({"<f4", dt.str})
+
+        def vector(name, v, cls, typestrs):
+            """The device pointer of an optional integer output: a ``cls`` or a foreign 1-D vector of ``N`` entries."""
+            if isinstance(v, cls):
+                if v.n != N:
+                    raise ValueError(f"{name} of {v.n} entries: expected {N}")
+                return v.ptr
+            if not isinstance(v, runtime._DeviceVector) and hasattr(v, "__cuda_array_interface__"):
+                return runtime.foreign_vector(v, N, typestrs)[0]
+            raise ValueError(f"{name} must be a runtime.{cls.__name__} or a __cuda_array_interface__ object of typestr {typestrs}, not {type(v).__name__}")
+
+        if reward is None:
+            reward = runtime.DeviceMatrix(N, 1, dt)
+        if hasattr(reward, "__cuda_array_interface__") and not isinstance(reward, runtime.DeviceMatrix) and len(reward.__cuda_array_interface__["shape"]) == 1:
+            rptr, rdt = runtime.foreign_vector(reward, N, floats)[0], np.dtype(reward.__cuda_array_interface__["typestr"])
+        else:
+            where = self._matrix_arg("reward", reward, 1, writable=True)
+            if where is None:
+                raise ValueError(f"reward must be None, a runtime.DeviceMatrix or a __cuda_array_interface__ object, not {type(reward).__name__}")
+            rptr, ld, rdt = where
+            if ld != 1 and N > 1:
+                raise ValueError("reward must be contiguous")
+        if done is None:
+            done = runtime.DeviceMask(N)
+        dptr = vector("done", done, runtime.DeviceMask, runtime.MASK_TYPESTRS)
+        fptr = None if fired is None else vector("fired", fired, runtime.DeviceWords, ("<u4",))
+        sptr = None if steps is None else vector("steps", steps, runtime.DeviceIndices, runtime.INDEX_TYPESTRS)
+        max_steps = int(max_steps)
+        if steps is not None and max_steps <= 0:
+            raise ValueError(f"steps is given, and max_steps = {max_steps} is not positive")
+        tptr, tld, tdt = None, K, dt
+        if terms is not None:
+            if K == 0:
+                raise ValueError("terms is given, and the spec has no reward term")
+            where = self._matrix_arg("terms", terms, K, writable=True)
+            if where is None:
+                raise ValueError(f"terms must be a runtime.DeviceMatrix or a 2-D __cuda_array_interface__ object, not {type(terms).__name__}")
+            tptr, tld, tdt = where
+        rep = self.velocity_representation if spec.velocity_representation is None else spec.velocity_representation
+        dm = _device_model_fast(self._model_ref, self.dtype)
+        ptrs = (C.c_void_p * 4)(*[b.ptr for b in blocks])
+        _lib.check(
+            _lib.load().jxs_env_evaluate(dm.handle, spec._table(dm), st.ptr, ptrs, N, int(rep), rptr, _lib.dtype_code(rdt), dptr, fptr, tptr,
+                                         _lib.dtype_code(tdt), tld, sptr, max_steps, runtime._sp()),
+            "jxs_env_evaluate",
+        )  # fmt: skip
+        return reward, done
+
 
 def random_model_data(
     model,
@@ -837,6 +921,71 @@ class _SpecTable:
                 pass
 
 
+def _term_slots(model, lay: StateLayout, term, name: str, opts: dict, src_names: list, src_rows: list, what: str):
+    """``(slots, default key)`` of one named term of an ``ObservationSpec`` or a ``RewardSpec``: the ``(kind, source, index)``
+    triples it stands for.  The options it understands are taken out of ``opts`` (``joints``; ``name``, ``rows``, ``take``);
+    a source new to ``src_names`` / ``src_rows`` is appended to them.  ``ValueError`` for an unknown name, joint or row."""
+    n = lay.n_joints
+    state = lambda first, count: [(OBS_STATE_ROW, 0, first + k) for k in range(count)]  # noqa: E731
+    kind = lambda k, comps: [(k, 0, c) for c in comps]  # noqa: E731
+    fixed = {
+        "base_position": state(lay.row_pos, 3),
+        "base_height": state(lay.row_pos + 2, 1),
+        "base_quaternion": state(lay.row_quat, 4),
+        "base_orientation": kind(OBS_BASE_QUAT_UNIT, range(4)),
+        "base_rotation": kind(OBS_BASE_ROTATION, range(9)),
+        "base_velocity": kind(OBS_BASE_VELOCITY, range(6)),
+        "base_linear_velocity": kind(OBS_BASE_VELOCITY, range(3)),
+        "base_angular_velocity": kind(OBS_BASE_VELOCITY, range(3, 6)),
+        "projected_gravity": kind(OBS_PROJECTED_GRAVITY, range(3)),
+        "tangential_deformation": state(lay.row_m, 3 * lay.n_points),
+    }
+    if name in ("joint_positions", "joint_velocities"):
+        first = lay.row_s if name == "joint_positions" else lay.row_sd
+        joints = opts.pop("joints", None)
+        if joints is None:
+            idx = list(range(n))
+        else:
+            known = {nm: i for i, nm in enumerate(model.joint_names())}
+            missing = [j for j in joints if j not in known]
+            if missing:
+                raise ValueError(f"term {name!r}: unknown joints {missing}")
+            idx = [known[j] for j in joints]
+        return [(OBS_STATE_ROW, 0, first + i) for i in idx], name
+    if name == "source":
+        sname, rows = opts.pop("name", None), opts.pop("rows", None)
+        if not isinstance(sname, str) or not isinstance(rows, (int, np.integer)) or rows <= 0:
+            raise ValueError(f"term {term!r}: a source needs name=<str> and rows=<positive int>")
+        take = opts.pop("take", None)
+        take = list(range(int(rows))) if take is None else [int(r) for r in take]
+        if any(r < 0 or r >= rows for r in take):
+            raise ValueError(f"source {sname!r}: rows {take} outside [0, {rows})")
+        if sname in src_names:
+            if src_rows[src_names.index(sname)] != int(rows):
+                raise ValueError(f"source {sname!r} named with {rows} and with {src_rows[src_names.index(sname)]} rows")
+        else:
+            if len(src_names) == OBS_MAX_SOURCES:
+                raise ValueError(f"more than {OBS_MAX_SOURCES} sources")
+            src_names.append(sname)
+            src_rows.append(int(rows))
+        return [(OBS_SOURCE_ROW, src_names.index(sname), r) for r in take], sname
+    if name in fixed:
+        return fixed[name], name
+    raise ValueError(f"unknown {what} term {name!r}")
+
+
+def _per_element(name: str, what: str, value, count: int, dt) -> np.ndarray:
+    """The option ``what`` of the term ``name`` as ``count`` float64 values (a scalar is repeated), each finite in ``dt``."""
+    a = np.asarray(value, dtype=np.float64)
+    if a.ndim > 1 or (a.ndim == 1 and a.shape[0] != count):
+        raise ValueError(f"term {name!r}: {what} of shape {a.shape}: expected a scalar or {count} values")
+    a = np.broadcast_to(a, (count,))
+    with np.errstate(over="ignore"):
+        if not (np.isfinite(a).all() and np.isfinite(a.astype(dt)).all()):
+            raise ValueError(f"term {name!r}: {what} is not finite in {dt.name}")
+    return a
+
+
 class ObservationSpec(_SpecTable):
     """What ``JaxSimModelData.observe`` assembles for one model: an ordered list of terms, flattened into ``size`` slots
     ``(kind, source, index)`` with an offset and a scale each (the table of ``jxs_observation_create``).  Built once on the
@@ -885,21 +1034,6 @@ class ObservationSpec(_SpecTable):
             raise ValueError(f"out_dtype {odt}: expected float32 or {dt}")
         if velocity_representation is not None:
             velocity_representation = VelRepr(velocity_representation)
-        n = lay.n_joints
-        state = lambda first, count: [(OBS_STATE_ROW, 0, first + k) for k in range(count)]  # noqa: E731
-        kind = lambda k, comps: [(k, 0, c) for c in comps]  # noqa: E731
-        fixed = {
-            "base_position": state(lay.row_pos, 3),
-            "base_height": state(lay.row_pos + 2, 1),
-            "base_quaternion": state(lay.row_quat, 4),
-            "base_orientation": kind(OBS_BASE_QUAT_UNIT, range(4)),
-            "base_rotation": kind(OBS_BASE_ROTATION, range(9)),
-            "base_velocity": kind(OBS_BASE_VELOCITY, range(6)),
-            "base_linear_velocity": kind(OBS_BASE_VELOCITY, range(3)),
-            "base_angular_velocity": kind(OBS_BASE_VELOCITY, range(3, 6)),
-            "projected_gravity": kind(OBS_PROJECTED_GRAVITY, range(3)),
-            "tangential_deformation": state(lay.row_m, 3 * lay.n_points),
-        }
         slots, offset, scale, slices, src_names, src_rows = [], [], [], {}, [], []
         if isinstance(terms, (str, bytes)):
             raise ValueError("terms must be a sequence of names or (name, options), not one string")
@@ -912,55 +1046,13 @@ class ObservationSpec(_SpecTable):
                 raise ValueError(f"term {term!r}: expected a name or (name, options)")
             key = opts.pop("key", None)
             t_scale, t_offset = opts.pop("scale", 1.0), opts.pop("offset", 0.0)
-            if name in ("joint_positions", "joint_velocities"):
-                first = lay.row_s if name == "joint_positions" else lay.row_sd
-                joints = opts.pop("joints", None)
-                if joints is None:
-                    idx = list(range(n))
-                else:
-                    known = {nm: i for i, nm in enumerate(model.joint_names())}
-                    missing = [j for j in joints if j not in known]
-                    if missing:
-                        raise ValueError(f"term {name!r}: unknown joints {missing}")
-                    idx = [known[j] for j in joints]
-                mine = [(OBS_STATE_ROW, 0, first + i) for i in idx]
-            elif name == "source":
-                sname, rows = opts.pop("name", None), opts.pop("rows", None)
-                if not isinstance(sname, str) or not isinstance(rows, (int, np.integer)) or rows <= 0:
-                    raise ValueError(f"term {term!r}: a source needs name=<str> and rows=<positive int>")
-                take = opts.pop("take", None)
-                take = list(range(int(rows))) if take is None else [int(r) for r in take]
-                if any(r < 0 or r >= rows for r in take):
-                    raise ValueError(f"source {sname!r}: rows {take} outside [0, {rows})")
-                if sname in src_names:
-                    if src_rows[src_names.index(sname)] != int(rows):
-                        raise ValueError(f"source {sname!r} named with {rows} and with {src_rows[src_names.index(sname)]} rows")
-                else:
-                    if len(src_names) == OBS_MAX_SOURCES:
-                        raise ValueError(f"more than {OBS_MAX_SOURCES} sources")
-                    src_names.append(sname)
-                    src_rows.append(int(rows))
-                mine = [(OBS_SOURCE_ROW, src_names.index(sname), r) for r in take]
-                key = sname if key is None else key
-            elif name in fixed:
-                mine = fixed[name]
-            else:
-                raise ValueError(f"unknown observation term {name!r}")
+            mine, default_key = _term_slots(model, lay, term, name, opts, src_names, src_rows, "observation")
+            key = default_key if key is None else key
             if opts:
                 raise ValueError(f"term {name!r}: unknown options {sorted(opts)}")
-            key = name if key is None else key
             if key in slices:
                 raise ValueError(f"two terms under the key {key!r}: give one of them the option key=")
-            vals = []
-            for what, v in (("scale", t_scale), ("offset", t_offset)):
-                a = np.asarray(v, dtype=np.float64)
-                if a.ndim > 1 or (a.ndim == 1 and a.shape[0] != len(mine)):
-                    raise ValueError(f"term {name!r}: {what} of shape {a.shape}: expected a scalar or {len(mine)} values")
-                a = np.broadcast_to(a, (len(mine),))
-                with np.errstate(over="ignore"):
-                    if not (np.isfinite(a).all() and np.isfinite(a.astype(dt)).all()):
-                        raise ValueError(f"term {name!r}: {what} is not finite in {dt.name}")
-                vals.append(a)
+            vals = [_per_element(name, what, v, len(mine), dt) for what, v in (("scale", t_scale), ("offset", t_offset))]
             slices[key] = slice(len(slots), len(slots) + len(mine))
             slots += mine
             scale += list(vals[0])
@@ -1145,3 +1237,235 @@ class ActionSpec(_SpecTable):
                                           self.params.ctypes.data_as(C.POINTER(C.c_double)), C.byref(handle)),
             "jxs_action_create",
         )  # fmt: skip
+
+
+# inners, outers and condition kinds of an evaluation table (JXS_EVAL_* of include/jaxsim_amd.h), the bits of the done byte
+EVAL_INNERS = {"identity": 0, "abs": 1, "square": 2, "excess": 3}
+EVAL_OUTERS = {"identity": 0, "exp": 1}
+EVAL_KINDS = {"terminated": 0, "truncated": 1}
+EVAL_MAX_SLOTS, EVAL_MAX_TERMS, EVAL_MAX_CONDITIONS = 1024, 32, 32
+DONE_TERMINATED, DONE_TRUNCATED = 1, 2
+
+
+class RewardSpec(_SpecTable):
+    """What ``JaxSimModelData.evaluate`` computes for one model: named reward terms and termination conditions over slots
+    ``(kind, source, index)`` with an offset, a scale and optionally a target each (the table of ``jxs_evaluation_create``).
+    Built once on the host -- no device is needed --, uploaded at the first ``evaluate``, used for every step of a loop.
+
+    ``slots`` ``[D, 3]`` / ``targets`` ``[D, 2]`` int32, ``offset`` / ``scale`` ``[D]`` float64, ``terms`` ``[K, 4]`` int32 =
+    first, count, inner, outer with ``term_params`` ``[K, 3]`` = weight, lo, hi, ``conditions`` ``[C, 2]`` int32 = slot, kind with
+    ``condition_limits`` ``[C, 2]`` = lo, hi.  ``term_names`` name the columns of ``evaluate(terms=)``, ``condition_names`` the
+    bits of ``evaluate(fired=)``, ``names`` is both; ``source_names`` / ``source_rows``: the blocks ``evaluate`` must be given."""
+
+    def __init__(self, layout: StateLayout, dtype, velocity_representation, slots, targets, offset, scale, terms, term_params, conditions,
+                 condition_limits, reward_clip, termination_reward, term_names, condition_names, source_names, source_rows):  # fmt: skip
+        self.layout = layout
+        self.dtype = np.dtype(dtype)
+        self.velocity_representation = None if velocity_representation is None else VelRepr(velocity_representation)
+        self.slots = np.ascontiguousarray(slots, dtype=np.int32).reshape(-1, 3)
+        self.targets = np.ascontiguousarray(targets, dtype=np.int32).reshape(-1, 2)
+        self.offset = np.ascontiguousarray(offset, dtype=np.float64)
+        self.scale = np.ascontiguousarray(scale, dtype=np.float64)
+        self.terms = np.ascontiguousarray(terms, dtype=np.int32).reshape(-1, 4)
+        self.term_params = np.ascontiguousarray(term_params, dtype=np.float64).reshape(-1, 3)
+        self.conditions = np.ascontiguousarray(conditions, dtype=np.int32).reshape(-1, 2)
+        self.condition_limits = np.ascontiguousarray(condition_limits, dtype=np.float64).reshape(-1, 2)
+        self.reward_clip = (float(reward_clip[0]), float(reward_clip[1]))
+        self.termination_reward = float(termination_reward)
+        self.term_names, self.condition_names = tuple(term_names), tuple(condition_names)
+        self.names = self.term_names + self.condition_names
+        self.source_names, self.source_rows = tuple(source_names), tuple(int(r) for r in source_rows)
+
+    @property
+    def n_terms(self) -> int:
+        return self.terms.shape[0]
+
+    @property
+    def n_conditions(self) -> int:
+        return self.conditions.shape[0]
+
+    @staticmethod
+    def build(model, rewards=(), terminations=(), *, reward_clip=(-np.inf, np.inf), termination_reward=0.0, dtype=np.float32,
+              velocity_representation=None) -> "RewardSpec":  # fmt: skip
+        """``rewards``: an ordered sequence of ``(name, options)``, at most 32.  ``term=`` names what the term reads, by the names
+        of ``ObservationSpec.build`` (``"joint_positions"`` / ``"joint_velocities"`` with ``joints=[names]``, ``"base_height"``,
+        ``"projected_gravity"``, ``"base_velocity"`` ..., or ``("source", dict(name=, rows=, take=))``); ``index=`` (an int or a
+        list) picks elements of it; ``offset=`` and ``scale=`` are a scalar or one value per element.  With ``y = (x - offset) *
+        scale`` of every element the term contributes
+
+            clip(weight * outer(sum inner(y)), *clip)
+
+        ``inner``: ``"identity"``, ``"abs"``, ``"square"`` or ``"excess"`` (``max(|y| - 1, 0)``); ``outer``: ``"identity"`` or
+        ``"exp"`` (``exp(-sum)``); ``weight`` defaults to 1, ``clip=(lo, hi)`` to no limits.  ``sigma`` divides the scales -- for
+        ``"square"`` by ``sqrt(sigma)``, so that ``outer="exp"`` gives ``exp(-sum (d / sqrt(sigma))^2)``.  ``target=("source",
+        dict(name=, rows=, row=))`` subtracts row ``row`` (an int, or one per element) of a source block from ``x`` first: the
+        commanded value of the environment.  ``inner="excess"`` on ``"joint_positions"`` without ``offset`` and ``scale`` takes
+        the model's position limits (``ActionSpec``'s ``clip_to_position_limits``): the term is how far, in half-ranges, each
+        joint lies outside them.
+
+        ``terminations``: ``(name, dict(term=, index=, offset=, scale=, target=, below=, above=, kind=))``, at most 32 elements
+        in all: the condition fires when ``y < below`` or ``y > above`` or ``y`` is NaN and sets ``kind`` (``"terminated"``, the
+        default, or ``"truncated"``) in the done byte.  A term of several elements gives one condition per element, named
+        ``name[i]``.
+
+        The reward is ``clip(sum of the terms, *reward_clip)``, plus ``termination_reward`` where a ``"terminated"`` condition
+        fired.  ``ValueError`` for an unknown term, option, joint, inner, outer or kind, a name used twice, a value that is not
+        finite in ``dtype``, ``lo > hi``, a ``sigma`` that is not positive, infinite joint limits, more than four sources, no
+        element at all or more than 1024."""
+        lay = StateLayout.of(model)
+        dt = np.dtype(dtype)
+        _lib.dtype_code(dt)
+        if velocity_representation is not None:
+            velocity_representation = VelRepr(velocity_representation)
+        src_names, src_rows = [], []
+        slots, targets, offset, scale = [], [], [], []
+
+        def finite(v) -> bool:
+            with np.errstate(over="ignore"):
+                return bool(np.isfinite(v) and np.isfinite(np.float64(v).astype(dt)))
+
+        def limits(name, what, pair):
+            if not isinstance(pair, (tuple, list)) or len(pair) != 2:
+                raise ValueError(f"{name!r}: {what} must be a pair (lo, hi)")
+            lo, hi = float(pair[0]), float(pair[1])
+            if not (lo <= hi and all(np.isinf(v) or finite(v) for v in (lo, hi))):
+                raise ValueError(f"{name!r}: {what} = ({lo}, {hi}): expected lo <= hi, each infinite or finite in {dt.name}")
+            return lo, hi
+
+        def entries(what, seq):
+            if isinstance(seq, (str, bytes, dict)):
+                raise ValueError(f"{what} must be a sequence of (name, options)")
+            seen = []
+            for item in seq:
+                if not (isinstance(item, (tuple, list)) and len(item) == 2 and isinstance(item[0], str) and isinstance(item[1], dict)):
+                    raise ValueError(f"{what}: {item!r}: expected (name, options)")
+                seen.append((item[0], dict(item[1])))
+            return seen
+
+        def elements(name, opts, inner=None):
+            """The slots of an entry with their offset, scale and target; the options used are taken out of ``opts``."""
+            term = opts.pop("term", None)
+            if isinstance(term, str):
+                tname, topts = term, {}
+            elif isinstance(term, (tuple, list)) and len(term) == 2 and isinstance(term[0], str) and isinstance(term[1], dict):
+                tname, topts = term[0], dict(term[1])
+            else:
+                raise ValueError(f"{name!r}: term = {term!r}: expected a name or (name, options)")
+            if "joints" in opts:
+                topts["joints"] = opts.pop("joints")
+            mine, _ = _term_slots(model, lay, term, tname, topts, src_names, src_rows, "reward")
+            if topts:
+                raise ValueError(f"{name!r}: term {tname!r}: unknown options {sorted(topts)}")
+            index = opts.pop("index", None)
+            if index is not None:
+                picks = [int(index)] if np.ndim(index) == 0 else [int(i) for i in index]
+                if any(i < 0 or i >= len(mine) for i in picks):
+                    raise ValueError(f"{name!r}: index {picks} outside [0, {len(mine)})")
+                mine = [mine[i] for i in picks]
+            if not mine:
+                raise ValueError(f"{name!r}: the term has no element")
+            t_offset, t_scale = opts.pop("offset", None), opts.pop("scale", None)
+            if inner == "excess" and tname == "joint_positions" and t_offset is None and t_scale is None:
+                kdp = model.kin_dyn_parameters
+                lo_all, hi_all = np.asarray(kdp.position_limits_min, dtype=float), np.asarray(kdp.position_limits_max, dtype=float)
+                j = [s[2] - lay.row_s for s in mine]
+                lo, hi = lo_all[j], hi_all[j]
+                if not (np.isfinite(lo).all() and np.isfinite(hi).all() and (hi > lo).all()):
+                    raise ValueError(f"{name!r}: the position limits of some named joint are infinite or empty")
+                t_offset, t_scale = (lo + hi) / 2, 2.0 / (hi - lo)
+            sc = _per_element(name, "scale", 1.0 if t_scale is None else t_scale, len(mine), dt)
+            off = _per_element(name, "offset", 0.0 if t_offset is None else t_offset, len(mine), dt)
+            tg = opts.pop("target", None)
+            mine_targets = [(-1, 0)] * len(mine)
+            if tg is not None:
+                if not (isinstance(tg, (tuple, list)) and len(tg) == 2 and tg[0] == "source" and isinstance(tg[1], dict)):
+                    raise ValueError(f"{name!r}: target = {tg!r}: expected ('source', dict(name=, rows=, row=))")
+                gopts = dict(tg[1])
+                row = gopts.pop("row", None)
+                if row is None:
+                    raise ValueError(f"{name!r}: a target needs row=")
+                rows_of = [int(row)] * len(mine) if np.ndim(row) == 0 else [int(r) for r in row]
+                if len(rows_of) != len(mine):
+                    raise ValueError(f"{name!r}: {len(rows_of)} target rows for {len(mine)} elements")
+                gopts["take"] = rows_of
+                got, _ = _term_slots(model, lay, tg, "source", gopts, src_names, src_rows, "reward")
+                if gopts:
+                    raise ValueError(f"{name!r}: target: unknown options {sorted(gopts)}")
+                mine_targets = [(s, r) for _, s, r in got]
+            return mine, off, sc, mine_targets
+
+        def choice(name, what, value, table):
+            if not isinstance(value, str) or value not in table:
+                raise ValueError(f"{name!r}: unknown {what} {value!r}: expected one of {sorted(table)}")
+            return table[value]
+
+        terms, term_params, term_names = [], [], []
+        for name, opts in entries("rewards", rewards):
+            inner_name, outer_name = opts.pop("inner", "identity"), opts.pop("outer", "identity")
+            inner, outer = choice(name, "inner", inner_name, EVAL_INNERS), choice(name, "outer", outer_name, EVAL_OUTERS)
+            mine, off, sc, tg = elements(name, opts, inner_name)
+            sigma = opts.pop("sigma", None)
+            if sigma is not None:
+                sigma = float(sigma)
+                if not (sigma > 0 and np.isfinite(sigma)):
+                    raise ValueError(f"{name!r}: sigma = {sigma}: expected a positive number")
+                sc = _per_element(name, "scale / sigma", sc / (np.sqrt(sigma) if inner_name == "square" else sigma), len(mine), dt)
+            weight = float(opts.pop("weight", 1.0))
+            if not finite(weight):
+                raise ValueError(f"{name!r}: weight = {weight} is not finite in {dt.name}")
+            lo, hi = limits(name, "clip", opts.pop("clip", (-np.inf, np.inf)))
+            if opts:
+                raise ValueError(f"{name!r}: unknown options {sorted(opts)}")
+            terms.append((len(slots), len(mine), inner, outer))
+            term_params.append((weight, lo, hi))
+            term_names.append(name)
+            slots += mine
+            targets += tg
+            offset += list(off)
+            scale += list(sc)
+        conditions, condition_limits, condition_names = [], [], []
+        for name, opts in entries("terminations", terminations):
+            kind = choice(name, "kind", opts.pop("kind", "terminated"), EVAL_KINDS)
+            mine, off, sc, tg = elements(name, opts)
+            lo, hi = limits(name, "(below, above)", (opts.pop("below", -np.inf), opts.pop("above", np.inf)))
+            if opts:
+                raise ValueError(f"{name!r}: unknown options {sorted(opts)}")
+            for i in range(len(mine)):
+                conditions.append((len(slots) + i, kind))
+                condition_limits.append((lo, hi))
+                condition_names.append(name if len(mine) == 1 else f"{name}[{i}]")
+            slots += mine
+            targets += tg
+            offset += list(off)
+            scale += list(sc)
+        names = term_names + condition_names
+        if len(set(names)) != len(names):
+            raise ValueError("a name is used twice")
+        if len(terms) > EVAL_MAX_TERMS or len(conditions) > EVAL_MAX_CONDITIONS:
+            raise ValueError(f"{len(terms)} terms and {len(conditions)} conditions: at most {EVAL_MAX_TERMS} and {EVAL_MAX_CONDITIONS}")
+        if not 1 <= len(slots) <= EVAL_MAX_SLOTS:
+            raise ValueError(f"a table of {len(slots)} elements: expected 1 .. {EVAL_MAX_SLOTS}")
+        clip = limits("reward_clip", "reward_clip", reward_clip)
+        if not finite(termination_reward):
+            raise ValueError(f"termination_reward = {termination_reward} is not finite in {dt.name}")
+        return RewardSpec(lay, dt, velocity_representation, slots, targets, offset, scale, terms, term_params, conditions, condition_limits, clip,
+                          termination_reward, term_names, condition_names, src_names, src_rows)  # fmt: skip
+
+    _destroy = "jxs_evaluation_destroy"
+
+    def _desc(self):
+        """The ``jxs_evaluation_desc`` of this spec; its pointers are into this object's arrays."""
+        d = _lib.EvaluationDesc()
+        d.D, d.K, d.C = self.slots.shape[0], self.n_terms, self.n_conditions
+        i32, f64 = C.POINTER(C.c_int32), C.POINTER(C.c_double)
+        d.slots, d.targets = self.slots.ctypes.data_as(i32), self.targets.ctypes.data_as(i32)
+        d.offset, d.scale = self.offset.ctypes.data_as(f64), self.scale.ctypes.data_as(f64)
+        d.terms, d.term_params = self.terms.ctypes.data_as(i32), self.term_params.ctypes.data_as(f64)
+        d.conditions, d.condition_limits = self.conditions.ctypes.data_as(i32), self.condition_limits.ctypes.data_as(f64)
+        d.reward_lo, d.reward_hi = self.reward_clip
+        d.termination_reward = self.termination_reward
+        d.source_rows = (C.c_int32 * 4)(*(list(self.source_rows) + [0] * (4 - len(self.source_rows))))
+        return d
+
+    def _create(self, dm, handle) -> None:
+        _lib.check(_lib.load().jxs_evaluation_create(dm.handle, C.byref(self._desc()), C.byref(handle)), "jxs_evaluation_create")

@@ -349,6 +349,16 @@ class DeviceIndices(_DeviceVector):
         return self._download()
 
 
+class DeviceWords(_DeviceVector):
+    """``N`` uint32 words on the device, one per environment: the ``fired`` output of ``JaxSimModelData.evaluate`` (bit ``c``:
+    condition ``c`` fired).  (Its int32 episode counters are a ``DeviceIndices``.)"""
+
+    typestr = "<u4"
+
+    def to_host(self) -> np.ndarray:
+        return self._download()
+
+
 def host_mask(mask, n: int) -> np.ndarray:
     """A host mask (bool or integer array or sequence of ``n`` entries; a scalar for ``n == 1``) as ``n`` bytes of 0 / 1.
     ``ValueError`` for another length or a non-boolean, non-integer dtype."""

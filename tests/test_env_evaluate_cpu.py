@@ -1,0 +1,494 @@
+"""The reward and the termination flags on the host: the harness (tests/env_evaluate_emul.py: jxs_eval::evaluate_env of
+jaxsim_amd/csrc/jxs_env_evaluate.h over every environment) against the NumPy restatement (tests/env_evaluate_ref.py) -- bit for
+bit for the + - x kinds, within 4 eps for an exponential on them, within bounds from the operation count against the float64
+truth for the derived kinds --, the special words, the counter, the validity check of a table, the refusals of the entry points
+that need no device, and the host logic of ``js.data.RewardSpec`` / ``JaxSimModelData.evaluate``."""
+
+import ctypes as C
+import dataclasses
+
+import numpy as np
+import pytest
+
+import env_evaluate_emul as emul
+import env_evaluate_ref as ref
+import env_observe_ref as oref
+import jaxsim_amd.api as js
+from jaxsim_amd import _lib, runtime
+from jaxsim_amd.model import VelRepr
+from jaxsim_amd.state import StateLayout
+from test_env_observe_cpu import make_block, same_or_both_nan, tiled_sources
+from test_env_ops_cpu import Foreign, lib, refused, stub_data  # noqa: F401  (lib: a fixture)
+
+DTYPES = (np.float32, np.float64)
+SHAPES = ((23, 32), (12, 4), (2, 0), (1, 3))  # (n_joints, n_points)
+TILES = (1, 2, 4)
+REPRS = (oref.INERTIAL, oref.BODY, oref.MIXED)
+SOURCE_ROWS = (5, 0, 3)  # sources 0 and 2; source 1 does not exist
+GRID = [pytest.param(n, npt, T, dt, id=f"n{n}-p{npt}-T{T}-{np.dtype(dt).name}") for n, npt in SHAPES for T in TILES for dt in DTYPES]
+S, SRC, VEL, GRAV, ROT, QUAT = oref.STATE_ROW, oref.SOURCE_ROW, oref.BASE_VELOCITY, oref.PROJECTED_GRAVITY, oref.BASE_ROTATION, oref.BASE_QUAT_UNIT
+
+
+def batch_sizes(T):
+    return sorted({1, T - 1, T + 1, 9 * T + 1} - {0})
+
+
+def make_sources(N, dtype, seed):
+    rng = np.random.default_rng(seed + 1)
+    return [None if r == 0 else rng.uniform(-3.0, 3.0, size=(r, N)).astype(dtype) for r in SOURCE_ROWS]
+
+
+def term_list(n, seed):
+    """Every inner, both outers, targets, finite and infinite clips, a one-slot term and an n-slot term (23 for the humanoid)."""
+    rng = np.random.default_rng(seed)
+    q, qd = [(S, 0, 7 + j) for j in range(n)], [(S, 0, 13 + n + j) for j in range(n)]
+    terms = [
+        dict(slots=q, inner=ref.EXCESS, offset=rng.uniform(-0.3, 0.3, n), scale=rng.uniform(1.5, 3.0, n), weight=-2.0),
+        dict(slots=qd, inner=ref.SQUARE, weight=-0.01, lo=-0.5),
+        dict(slots=[(S, 0, 2)], offset=0.5, weight=1.5),
+        dict(slots=[(SRC, 0, k) for k in range(3)], inner=ref.ABS, target=[(2, k) for k in range(3)], hi=2.0, weight=0.7),
+        dict(slots=[(VEL, 0, k) for k in range(3)], inner=ref.SQUARE, outer=ref.OUTER_EXP, target=[(0, k) for k in range(3)], scale=0.5),
+        dict(slots=qd[:2], inner=ref.SQUARE, outer=ref.OUTER_EXP, scale=0.3, weight=0.5, offset=0.1),
+        dict(slots=[(GRAV, 0, 0), (GRAV, 0, 1)], inner=ref.SQUARE, weight=-1.0),
+        dict(slots=[(ROT, 0, 8)], weight=0.25, lo=-0.1, hi=0.2),
+        dict(slots=[(QUAT, 0, 0)], inner=ref.ABS, scale=2.0),
+        dict(slots=[(VEL, 0, k) for k in range(3, 6)], inner=ref.ABS, lo=-1.0, hi=1.0, weight=0.1),
+        dict(slots=[(SRC, 2, 1), (S, 0, 0)], inner=ref.IDENTITY, outer=ref.OUTER_EXP, scale=0.2, weight=-0.3),
+    ]
+    return [t for t in terms if len(t["slots"])]  # (a model without joints has no joint terms)
+
+
+def gap_threshold(values, bound):
+    """A threshold in the widest gap of the finite ``values``, and the distance from it to the nearest of them over ``bound``."""
+    v = np.sort(values[np.isfinite(values)])
+    if len(v) < 2:
+        return (float(v[0]) + 1.0 if len(v) else 0.0), np.inf
+    k = int(np.argmax(np.diff(v)))
+    return float((v[k] + v[k + 1]) / 2), float((v[k + 1] - v[k]) / 2 / max(bound, 1e-300))
+
+
+def cond_list(n, blk, srcs, repr_):
+    """Windows on exact kinds, and thresholds on derived kinds placed in the widest gap of the batch's float64 values."""
+    conds = [
+        dict(slot=(S, 0, 2), lo=-0.5, hi=0.8),
+        dict(slot=(SRC, 2, 1), hi=2.0, kind=ref.KIND_TRUNCATED),
+        dict(slot=(S, 0, 7 if n else 1), offset=0.1, scale=1.7, lo=-1.0, hi=1.0),
+        dict(slot=(SRC, 0, 4), target=(2, 0), lo=-2.5, kind=ref.KIND_TRUNCATED),
+    ]
+    probe = ref.make_table(conds=[dict(slot=(GRAV, 0, 2)), dict(slot=(VEL, 0, 0), scale=0.5), dict(slot=(ROT, 0, 0), offset=0.25)])
+    y = ref.slot_words(blk, probe, n, repr_, srcs, dtype=np.float64)
+    b = ref.slot_bounds(blk, probe, n, repr_, srcs)
+    margins = []
+    for k, (slot, extra) in enumerate((((GRAV, 0, 2), {}), ((VEL, 0, 0), dict(scale=0.5)), ((ROT, 0, 0), dict(offset=0.25)))):
+        th, margin = gap_threshold(y[k], float(b[k][np.isfinite(b[k])].max(initial=0.0)))
+        margins.append(margin)
+        conds.append(dict(slot=slot, **extra, **({"hi": th} if k != 1 else {"lo": th}), kind=ref.KIND_TRUNCATED if k == 2 else ref.KIND_TERMINATED))
+    return conds, margins
+
+
+def emul_evaluate(storage, tb, rows, n, N, T, repr_, tsrcs, **kw):
+    return emul.evaluate(storage, tb, rows, n, N, T, repr_, sources=tsrcs, **kw)
+
+
+def check_against_the_restatement(evaluate, n, n_points, T, dtype, what, sizes=None, seed=0):
+    """``evaluate(storage, table, rows, n, N, T, repr, tiled sources, steps=, max_steps=, fill=)`` -> dict of outputs against
+    tests/env_evaluate_ref.py over the batch sizes and the three representations.  Returns the worst ratios."""
+    rows = oref.n_rows(n, n_points)
+    eps = float(np.finfo(dtype).eps)
+    worst = {"exp": 0.0, "derived": 0.0, "reward": 0.0}
+    for N in sizes or batch_sizes(T):
+        blk = make_block(n, n_points, N, dtype, seed=seed + 100 * N + rows)
+        srcs = make_sources(N, dtype, seed=N)
+        storage, tsrcs = oref.tile_block(blk, T, pad=np.nan), tiled_sources(srcs, T)
+        steps = np.random.default_rng(N).integers(0, 9, size=N).astype(np.int32)
+        for repr_ in REPRS:
+            tag = f"{what} N={N} repr={repr_}"
+            terms = term_list(n, seed=rows)
+            conds, margins = cond_list(n, blk, srcs, repr_)
+            # (the thresholds on derived kinds are clear of every environment's value by more than its bound: asserted for all)
+            assert min(margins) > 1.0, f"{tag}: a derived threshold lies within the bound of some environment: {margins}"
+            tb = ref.make_table(terms, conds, reward_clip=(-3.0, 2.5), termination_reward=-1.25)
+            exact, is_exp, is_derived = ref.term_classes(tb, repr_)
+            want = ref.evaluate(blk, tb, n, repr_, srcs, steps=steps, max_steps=7)
+            got = evaluate(storage, tb, rows, n, N, T, repr_, tsrcs, steps=steps, max_steps=7)
+            for k in ("done", "fired", "steps"):
+                assert np.array_equal(got[k], want[k]), f"{tag}: {k} {got[k]} != {want[k]}"
+            same_or_both_nan(got["terms"], want["terms"], np.broadcast_to(exact[None, :], (N, tb.K)), f"{tag} terms")
+            truth = ref.truth(blk, tb, n, repr_, srcs, steps=steps, max_steps=7)
+            assert np.array_equal(np.isnan(got["terms"]), np.isnan(truth["terms"])), f"{tag}: NaN terms"
+            with np.errstate(invalid="ignore"):
+                err = np.abs(got["terms"].astype(np.float64) - want["terms"].astype(np.float64))
+                rel = err / (4 * eps * np.abs(want["terms"].astype(np.float64)))
+                terr = np.abs(got["terms"].astype(np.float64) - truth["terms"]) / ref.bounds(blk, tb, n, repr_, srcs)
+            if is_exp.any():
+                r = float(np.nanmax(np.where(err[:, is_exp] == 0, 0.0, rel[:, is_exp])))
+                worst["exp"] = max(worst["exp"], r)
+                assert r <= 1.0, f"{tag}: an EXP term misses 4 eps |want| by a factor of {r:.3g}"
+            if is_derived.any():
+                r = float(np.nanmax(terr[:, is_derived]))
+                worst["derived"] = max(worst["derived"], r)
+                assert r <= 1.0, f"{tag}: a term on a derived kind misses its bound by a factor of {r:.3g}"
+            # the reward of the whole table: within the terms' bounds and the K roundings of the sum
+            tp = np.abs(truth["terms"])
+            rb = ref.bounds(blk, tb, n, repr_, srcs).sum(axis=1) + 2 * (tb.K + 1) * eps * (tp.sum(axis=1) + abs(tb.termination_reward))
+            with np.errstate(invalid="ignore"):
+                r = float(np.nanmax(np.abs(got["reward"].astype(np.float64) - truth["reward"]) / rb))
+            assert np.array_equal(np.isnan(got["reward"]), np.isnan(truth["reward"])), f"{tag}: NaN rewards"
+            worst["reward"] = max(worst["reward"], r)
+            assert r <= 1.0, f"{tag}: the reward misses its bound by a factor of {r:.3g}"
+            # the bit-exact terms alone: reward, terms, done, fired and steps bit for bit; into a wider terms row too
+            xt = ref.make_table([t for t, e in zip(terms, exact) if e], conds, reward_clip=(-3.0, 2.5), termination_reward=-1.25)
+            want = ref.evaluate(blk, xt, n, repr_, srcs, steps=steps, max_steps=7)
+            got = evaluate(storage, xt, rows, n, N, T, repr_, tsrcs, steps=steps, max_steps=7, terms_ld=xt.K + 3, fill=np.nan)
+            all_ = np.ones((N, xt.K), bool)
+            same_or_both_nan(got["reward"], want["reward"], all_[:, 0], f"{tag} exact reward")
+            same_or_both_nan(np.ascontiguousarray(got["terms"][:, : xt.K]), want["terms"], all_, f"{tag} exact terms")
+            assert np.isnan(got["terms"][:, xt.K :]).all(), f"{tag}: the gap columns of a wider terms row were written"
+            for k in ("done", "fired", "steps"):
+                assert np.array_equal(got[k], want[k]), f"{tag}: exact {k}"
+    return worst
+
+
+@pytest.mark.parametrize("n,n_points,T,dtype", GRID)
+def test_the_harness_equals_the_restatement(n, n_points, T, dtype):
+    """Bit for bit: ``done``, ``fired``, ``steps``, and ``reward`` / ``terms`` of the terms on state rows, source rows and the
+    Inertial or Mixed velocity with the identity outer.  ``EXP`` terms on such slots: ``|got - want| <= 4 eps |want|`` (two
+    exponentials documented to 1 ulp each, and the two roundings of the weight); measured worst ratio over this grid 0.47 (the
+    harness's exponential against NumPy's).  Terms on derived kinds against the float64 truth within
+    ``env_evaluate_ref.bounds``: worst ratio 0.04; the reward of the whole table against the sum of its terms' bounds: 0.01."""
+    worst = check_against_the_restatement(emul_evaluate, n, n_points, T, dtype, "harness")
+    print("worst ratios:", {k: round(v, 4) for k, v in worst.items()})
+
+
+def small_case(dtype, N=6, n=2, n_points=0, seed=5):
+    blk = make_block(n, n_points, N, dtype, seed=seed)
+    blk[7 + n // 2] = np.random.default_rng(seed).uniform(-1, 1, N).astype(dtype)  # (no NaN row here)
+    blk[3:7, N - 1] = blk[3:7, 0]
+    return blk, make_sources(N, dtype, seed)
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=lambda d: np.dtype(d).name)
+@pytest.mark.parametrize("K,C", [(0, 3), (3, 0), (32, 32), (32, 0), (0, 32)])
+def test_the_extreme_widths(dtype, K, C):
+    """``K = 0`` gives the reward 0 (the termination reward where an environment terminated), ``C = 0`` a zero ``done``;
+    ``K = 32`` with ``C = 32`` is the widest table."""
+    n, T, N = 2, 2, 5
+    rows = oref.n_rows(n, 0)
+    blk, srcs = small_case(dtype, N)
+    rng = np.random.default_rng(K + C)
+    terms = [dict(slots=[(S, 0, int(r)) for r in rng.integers(0, rows, size=1 + t % 3)], inner=t % 4, weight=float(rng.uniform(-1, 1))) for t in range(K)]
+    conds = [dict(slot=(S, 0, int(rng.integers(0, rows))), lo=-0.2 - 0.1 * c, kind=c % 2) for c in range(C)]
+    tb = ref.make_table(terms, conds, termination_reward=-2.0)
+    want = ref.evaluate(blk, tb, n, oref.MIXED, srcs)
+    got = emul.evaluate(oref.tile_block(blk, T, pad=np.nan), tb, rows, n, N, T, oref.MIXED, sources=tiled_sources(srcs, T), terms=K > 0)
+    same_or_both_nan(got["reward"], want["reward"], np.ones(N, bool), "reward")
+    assert np.array_equal(got["done"], want["done"]) and np.array_equal(got["fired"], want["fired"])
+    if K == 0:
+        assert np.array_equal(got["reward"], np.where(want["done"] & 1, dtype(-2.0), dtype(0.0)))
+    else:
+        same_or_both_nan(got["terms"], want["terms"], np.ones((N, K), bool), "terms")
+    if C == 0:
+        assert not got["done"].any() and not got["fired"].any()
+    if C == 32:
+        assert want["fired"].max() >= 1 << 31, "no environment fires the last condition: the case does not reach bit 31"
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=lambda d: np.dtype(d).name)
+def test_special_words_stay_where_they_are(dtype):
+    """NaN, +-inf and -0 in the rows a slot reads, in environments 0 .. 3: a NaN fires its condition and gives a NaN reward, the
+    others follow the comparisons.  NaN in every row no slot reads, in the padding columns and in the unread source rows reaches
+    no output."""
+    n, n_points, T, N = 12, 4, 4, 6
+    rows = oref.n_rows(n, n_points)
+    blk = make_block(n, n_points, N, dtype, seed=11)
+    blk[7 + n // 2] = 0.25  # (make_block's NaN row)
+    blk[3:7, N - 1] = blk[3:7, 0]
+    read_rows = [2, 8, 9, 13 + n]
+    terms = [dict(slots=[(S, 0, 8), (S, 0, 9)], inner=ref.SQUARE, weight=-1.0), dict(slots=[(S, 0, 13 + n)], inner=ref.ABS, weight=0.5),
+             dict(slots=[(SRC, 0, 1)], inner=ref.EXCESS, target=(2, 2))]  # fmt: skip
+    conds = [dict(slot=(S, 0, 2), lo=0.0, hi=100.0)]
+    tb = ref.make_table(terms, conds, termination_reward=-1.0)
+    srcs = make_sources(N, dtype, 3)
+    for e, word in enumerate((np.nan, np.inf, -np.inf, -0.0)):
+        blk[2, e] = word
+        blk[8, e] = word
+    unread = np.setdiff1d(np.arange(rows), read_rows + [3, 4, 5, 6])
+    dirty = blk.copy()
+    dirty[unread] = np.nan
+    dsrcs = [None if s is None else s.copy() for s in srcs]
+    dsrcs[0][[0, 2, 3, 4]] = np.nan
+    dsrcs[2][[0, 1]] = np.nan
+    want = ref.evaluate(blk, tb, n, oref.MIXED, srcs)
+    for b, ss in ((blk, srcs), (dirty, dsrcs)):
+        got = emul.evaluate(oref.tile_block(b, T, pad=np.nan), tb, rows, n, N, T, oref.MIXED, sources=tiled_sources(ss, T))
+        same_or_both_nan(got["reward"], want["reward"], np.ones(N, bool), "reward")
+        same_or_both_nan(got["terms"], want["terms"], np.ones((N, 3), bool), "terms")
+        assert np.array_equal(got["done"], want["done"]) and np.array_equal(got["fired"], want["fired"])
+        assert np.isnan(got["reward"][0]) and got["done"][0] == 1, "a NaN height fires its condition, a NaN slot gives a NaN reward"
+        assert got["done"][1] == 1 and got["done"][2] == 1 and got["done"][3] == 0  # (+inf above, -inf below, -0 inside [0, 100])
+        assert got["reward"][1] == -np.inf and got["reward"][2] == -np.inf  # (inf^2 weighted by -1, then the termination reward)
+        assert np.isfinite(got["reward"][3:]).all() and np.isfinite(got["terms"][3:]).all()
+
+
+def test_the_counter():
+    """``steps`` reaching ``max_steps`` sets TRUNCATED, no bit of ``fired``, and zeroes the counter; a terminated environment is
+    zeroed; the others are incremented; without ``steps`` nothing of it is written."""
+    n, T, N, dtype = 2, 2, 7, np.float32
+    rows = oref.n_rows(n, 0)
+    blk, srcs = small_case(dtype, N)
+    blk[2] = [0.5, 0.5, -1.0, 0.5, -1.0, 0.5, 0.5]  # (environments 2 and 4 fall below the height window)
+    tb = ref.make_table([dict(slots=[(S, 0, 2)])], [dict(slot=(S, 0, 2), lo=0.0)], termination_reward=-5.0)
+    steps = np.array([0, 5, 3, 6, 6, 2**31 - 1, -3], np.int32)
+    storage = oref.tile_block(blk, T, pad=np.nan)
+    got = emul.evaluate(storage, tb, rows, n, N, T, oref.MIXED, steps=steps, max_steps=7)
+    assert list(got["steps"]) == [1, 6, 0, 0, 0, -(2**31), -2]  # (a counter at INT32_MAX wraps instead of overflowing)
+    assert list(got["done"]) == [0, 0, 1, 2, 3, 0, 0] and list(got["fired"]) == [0, 0, 1, 0, 1, 0, 0]
+    assert list(got["reward"]) == [0.5, 0.5, -6.0, 0.5, -6.0, 0.5, 0.5]
+    want = ref.evaluate(blk, tb, n, oref.MIXED, srcs, steps=steps, max_steps=7)
+    assert np.array_equal(got["steps"], want["steps"]) and np.array_equal(got["done"], want["done"]) and np.array_equal(got["fired"], want["fired"])
+    for s, m, d in ((0, 1, 0), (5, 7, 0), (6, 7, 0), (6, 7, 1), (3, 7, 1), (3, 7, 2)):
+        n_, dn = emul.counted(s, m, d)
+        assert (n_, dn) == ((0, d | (2 if s + 1 >= m else 0)) if (d or s + 1 >= m) else (s + 1, 0))
+    plain = emul.evaluate(storage, tb, rows, n, N, T, oref.MIXED)
+    assert plain["steps"] is None and list(plain["done"]) == [0, 0, 1, 0, 1, 0, 0]
+    # one output alone; none at all, a counter without max_steps and a short terms row are not evaluated
+    only = emul.evaluate(storage, tb, rows, n, N, T, oref.MIXED, reward=False, fired=False, terms=False)
+    assert only["reward"] is None and list(only["done"]) == [0, 0, 1, 0, 1, 0, 0]
+    assert emul.evaluate(storage, tb, rows, n, N, T, oref.MIXED, reward=False, done=False, rc=True) == -2
+    assert emul.evaluate(storage, tb, rows, n, N, T, oref.MIXED, steps=steps, max_steps=0, rc=True) == -2
+    assert emul.evaluate(storage, tb, rows, n, N, T, oref.MIXED, terms_ld=0, rc=True) == -2
+
+
+def test_the_validity_check_of_a_table():
+    rows, src = 40, (5, 0, 3, 0)
+    terms = [dict(slots=[(S, 0, 0), (S, 0, rows - 1)], inner=ref.SQUARE), dict(slots=[(SRC, 0, 4)], target=(2, 2), outer=ref.OUTER_EXP),
+             dict(slots=[(VEL, 0, 5), (GRAV, 0, 2)], inner=ref.EXCESS, lo=-1.0, hi=1.0)]  # fmt: skip
+    conds = [dict(slot=(ROT, 0, 8), lo=-np.inf, hi=0.5), dict(slot=(S, 0, 3), kind=ref.KIND_TRUNCATED, target=(0, 0))]
+    good = ref.make_table(terms, conds, reward_clip=(-1.0, np.inf))
+    both = lambda tb, dtype=np.float32, **kw: (emul.table_error(tb, rows, src, dtype, **{("C_" if k == "C" else k): v for k, v in kw.items()}),
+                                               ref.table_error(tb, rows, src, dtype, **kw))  # noqa: E731  # fmt: skip
+    assert both(good) == ((ref.OK, -1), (ref.OK, -1))
+
+    def changed(field, index, value):
+        a = getattr(good, field).copy()
+        a[index] = value
+        return dataclasses.replace(good, **{field: a})
+
+    cases = [
+        (changed("slots", (1, 2), rows), ref.BAD_SLOT, 1), (changed("slots", (0, 0), 6), ref.BAD_SLOT, 0), (changed("slots", (2, 1), 1), ref.BAD_SLOT, 2),
+        (changed("slots", (3, 2), 6), ref.BAD_SLOT, 3), (changed("slots", (5, 2), 9), ref.BAD_SLOT, 5),
+        (changed("targets", (2, 0), 1), ref.BAD_TARGET, 2), (changed("targets", (2, 0), 4), ref.BAD_TARGET, 2), (changed("targets", (2, 0), -2), ref.BAD_TARGET, 2),
+        (changed("targets", (2, 1), 3), ref.BAD_TARGET, 2), (changed("targets", (6, 1), -1), ref.BAD_TARGET, 6),
+        (changed("offset", 4, np.inf), ref.NOT_FINITE, 4), (changed("scale", 0, np.nan), ref.NOT_FINITE, 0), (changed("scale", 1, 1e39), ref.NOT_FINITE, 1),
+        (changed("terms", (1, 2), 4), ref.BAD_TERM, 1), (changed("terms", (1, 2), -1), ref.BAD_TERM, 1), (changed("terms", (0, 3), 2), ref.BAD_TERM, 0),
+        (changed("terms", (1, 1), 0), ref.BAD_RANGE, 1), (changed("terms", (1, 0), 1), ref.BAD_RANGE, 1), (changed("terms", (2, 1), 5), ref.BAD_RANGE, 2),
+        (changed("terms", (0, 0), -1), ref.BAD_RANGE, 0), (changed("terms", (2, 1), 1), ref.UNOWNED, 4),
+        (changed("term_params", (1, 0), np.inf), ref.NOT_FINITE, 1), (changed("term_params", (0, 0), 1e39), ref.NOT_FINITE, 0),
+        (changed("term_params", (2, 1), 2.0), ref.BAD_LIMITS, 2), (changed("term_params", (2, 2), np.nan), ref.BAD_LIMITS, 2),
+        (changed("term_params", (2, 2), 1e39), ref.BAD_LIMITS, 2),
+        (changed("conds", (0, 1), 2), ref.BAD_CONDITION, 0), (changed("conds", (1, 0), 7), ref.BAD_CONDITION, 1), (changed("conds", (1, 0), 5), ref.BAD_CONDITION, 1),
+        (changed("conds", (0, 0), 2), ref.BAD_CONDITION, 0), (changed("cond_limits", (0, 0), 1.0), ref.BAD_LIMITS, 0),
+        (changed("cond_limits", (1, 1), np.nan), ref.BAD_LIMITS, 1),
+        (dataclasses.replace(good, reward_lo=1.0, reward_hi=0.0), ref.BAD_LIMITS, -1), (dataclasses.replace(good, reward_hi=np.nan), ref.BAD_LIMITS, -1),
+        (dataclasses.replace(good, termination_reward=np.inf), ref.NOT_FINITE, -1), (dataclasses.replace(good, termination_reward=-1e39), ref.NOT_FINITE, -1),
+    ]  # fmt: skip
+    for tb, code, at in cases:
+        assert both(tb) == ((code, at), (code, at)), (code, at, both(tb))
+    # what float64 holds and float32 does not
+    assert both(changed("scale", 1, 1e39), np.float64) == ((ref.OK, -1), (ref.OK, -1))
+    assert both(dataclasses.replace(good, termination_reward=-1e39), np.float64) == ((ref.OK, -1), (ref.OK, -1))
+    # the widths
+    for kw in (dict(D=0), dict(D=-1), dict(D=ref.MAX_SLOTS + 1), dict(K=-1), dict(K=ref.MAX_TERMS + 1), dict(C=-1), dict(C=ref.MAX_CONDITIONS + 1)):
+        e, r = both(good, **kw)
+        assert e[0] == r[0] == ref.BAD_WIDTH, kw
+    wide = ref.make_table([dict(slots=[(S, 0, 1)] * ref.MAX_SLOTS)])
+    assert both(wide) == ((ref.OK, -1), (ref.OK, -1))
+    assert both(ref.make_table([dict(slots=[(S, 0, 1)])] * 33))[0][0] == ref.BAD_WIDTH
+    # a source of a table without source rows
+    assert emul.table_error(ref.make_table([dict(slots=[(SRC, 0, 0)])]), rows, None)[0] == ref.BAD_SLOT
+    # an invalid table or a null source is not evaluated
+    blk, _ = small_case(np.float32, 3)
+    st = oref.tile_block(blk, 2)
+    assert emul.evaluate(st, ref.make_table([dict(slots=[(S, 0, blk.shape[0])])]), blk.shape[0], 2, 3, 2, oref.MIXED, rc=True) == -2
+    assert emul.evaluate(st, ref.make_table([dict(slots=[(S, 0, 0)], target=(0, 0))]), blk.shape[0], 2, 3, 2, oref.MIXED, sources=[None], rc=True) == -2
+
+
+def test_cabi_exports_and_refusals_without_a_device(lib):  # noqa: F811
+    for name in ("jxs_evaluation_create", "jxs_evaluation_destroy", "jxs_env_evaluate"):
+        assert name in _lib.EXPORTED_SYMBOLS and hasattr(lib, name)
+    p = C.c_void_p(0x1000)  # (never dereferenced: every call below is refused before the model is looked at)
+    h = C.c_void_p(0x2000)
+    desc = _lib.EvaluationDesc()
+    refused(lib, lib.jxs_evaluation_create(None, C.byref(desc), C.byref(h)), "null")
+    assert h.value is None  # (a refused creation hands back no table)
+    refused(lib, lib.jxs_evaluation_create(p, C.byref(desc), None), "null")
+    refused(lib, lib.jxs_evaluation_create(p, None, C.byref(h)), "null")
+    assert lib.jxs_evaluation_destroy(None) == 0
+    src = (C.c_void_p * 4)()
+    # jxs_env_evaluate(model, table, state, sources, N, repr, reward, reward_dtype, done, fired, terms, terms_dtype, terms_ld, steps, max_steps, stream)
+    good = [p, p, p, src, 3, 2, p, _lib.JXS_F32, p, None, None, _lib.JXS_F32, 0, None, 0, None]
+    for k in (0, 1, 2):  # model, table, state
+        args = list(good)
+        args[k] = None
+        refused(lib, lib.jxs_env_evaluate(*args), "jxs_env_evaluate: null")
+    args = list(good)
+    args[6] = args[8] = None
+    refused(lib, lib.jxs_env_evaluate(*args), "at least one")
+    for N in (0, -1):
+        args = list(good)
+        args[4] = N
+        refused(lib, lib.jxs_env_evaluate(*args), "positive")
+    for rep in (-1, 3):
+        args = list(good)
+        args[5] = rep
+        refused(lib, lib.jxs_env_evaluate(*args), "representation")
+
+
+# ---- host logic of the Python layer ---------------------------------------------------------------------------------
+def test_reward_spec_build(models):
+    icub = models("icub")
+    lay = StateLayout.of(icub)
+    n = lay.n_joints
+    names = list(icub.joint_names())
+    cmd = ("source", dict(name="command", rows=6, row=[0, 1, 2]))
+    spec = js.data.RewardSpec.build(
+        icub,
+        rewards=[
+            ("track_lin", dict(term="base_linear_velocity", target=cmd, inner="square", outer="exp", sigma=0.25, weight=1.5)),
+            ("upright", dict(term="projected_gravity", index=[0, 1], inner="square", weight=-2.0)),
+            ("joint_rate", dict(term="joint_velocities", inner="square", weight=-1e-3, scale=np.full(n, 2.0), clip=(-1.0, 0.0))),
+            ("torques", dict(term=("source", dict(name="tau", rows=n)), inner="abs", sigma=4.0)),
+            ("limits", dict(term="joint_positions", joints=[names[3], names[0]], inner="excess", weight=-5.0)),
+            ("height", dict(term="base_height", offset=0.6)),
+        ],
+        terminations=[
+            ("fell", dict(term="base_height", below=0.3)),
+            ("tilted", dict(term="projected_gravity", index=2, above=-0.5)),
+            ("wandered", dict(term="base_position", index=[0, 1], scale=0.5, below=-1.0, above=1.0, kind="truncated")),
+        ],
+        reward_clip=(-10.0, 10.0), termination_reward=-3.0, velocity_representation=VelRepr.Body,
+    )  # fmt: skip
+    assert spec.term_names == ("track_lin", "upright", "joint_rate", "torques", "limits", "height")
+    assert spec.condition_names == ("fell", "tilted", "wandered[0]", "wandered[1]") and spec.names == spec.term_names + spec.condition_names
+    assert spec.source_names == ("command", "tau") and spec.source_rows == (6, n)
+    assert spec.dtype == np.float32 and spec.velocity_representation == VelRepr.Body and spec.layout == lay
+    assert spec.n_terms == 6 and spec.n_conditions == 4 and spec.reward_clip == (-10.0, 10.0) and spec.termination_reward == -3.0
+    counts = [3, 2, n, n, 2, 1]
+    firsts = np.concatenate([[0], np.cumsum(counts)[:-1]])
+    inner, outer = js.data.EVAL_INNERS, js.data.EVAL_OUTERS
+    np.testing.assert_array_equal(spec.terms, [(f, c, i, o) for f, c, i, o in zip(
+        firsts, counts, [inner["square"], inner["square"], inner["square"], inner["abs"], inner["excess"], inner["identity"]],
+        [outer["exp"], 0, 0, 0, 0, 0])])  # fmt: skip
+    np.testing.assert_array_equal(spec.term_params, [(1.5, -np.inf, np.inf), (-2.0, -np.inf, np.inf), (-1e-3, -1.0, 0.0), (1.0, -np.inf, np.inf),
+                                                     (-5.0, -np.inf, np.inf), (1.0, -np.inf, np.inf)])  # fmt: skip
+    D = sum(counts)
+    np.testing.assert_array_equal(spec.slots[:3], [(VEL, 0, c) for c in range(3)])
+    np.testing.assert_array_equal(spec.targets[:3], [(0, 0), (0, 1), (0, 2)])
+    assert (spec.targets[3:, 0] == -1).all()
+    np.testing.assert_array_equal(spec.slots[3:5], [(GRAV, 0, 0), (GRAV, 0, 1)])
+    np.testing.assert_array_equal(spec.slots[firsts[3] : firsts[3] + n], [(SRC, 1, r) for r in range(n)])
+    np.testing.assert_array_equal(spec.slots[firsts[4] : firsts[4] + 2], [(S, 0, lay.row_s + 3), (S, 0, lay.row_s)])
+    np.testing.assert_array_equal(spec.slots[D:], [(S, 0, 2), (GRAV, 0, 2), (S, 0, 0), (S, 0, 1)])
+    np.testing.assert_array_equal(spec.conditions, [(D, 0), (D + 1, 0), (D + 2, 1), (D + 3, 1)])
+    np.testing.assert_array_equal(spec.condition_limits, [(0.3, np.inf), (-np.inf, -0.5), (-1.0, 1.0), (-1.0, 1.0)])
+    # sigma: the scales divided by sqrt(sigma) for a square, by sigma otherwise, in float64
+    np.testing.assert_array_equal(spec.scale[:3], 1.0 / np.sqrt(0.25))
+    np.testing.assert_array_equal(spec.scale[firsts[3] : firsts[3] + n], 1.0 / 4.0)
+    np.testing.assert_array_equal(spec.scale[firsts[2] : firsts[2] + n], 2.0)
+    # the joint-limit excess: centre and 1 / half-width of the model's position limits
+    kdp = icub.kin_dyn_parameters
+    lo, hi = np.asarray(kdp.position_limits_min, float)[[3, 0]], np.asarray(kdp.position_limits_max, float)[[3, 0]]
+    np.testing.assert_array_equal(spec.offset[firsts[4] : firsts[4] + 2], (lo + hi) / 2)
+    np.testing.assert_array_equal(spec.scale[firsts[4] : firsts[4] + 2], 2.0 / (hi - lo))
+    assert spec.offset[firsts[5]] == 0.6 and (spec.scale[D + 2 :] == 0.5).all()
+    # the table is valid by the harness's and the restatement's check
+    tb = ref.Table(spec.slots, spec.offset, spec.scale, spec.targets, spec.terms, spec.term_params, spec.conditions, spec.condition_limits,
+                   *spec.reward_clip, spec.termination_reward)  # fmt: skip
+    assert emul.table_error(tb, lay.n_rows, spec.source_rows) == ref.table_error(tb, lay.n_rows, spec.source_rows) == (ref.OK, -1)
+    # explicit offset / scale keep the excess as it is; conditions alone and terms alone are tables too
+    own = js.data.RewardSpec.build(icub, rewards=[("limits", dict(term="joint_positions", inner="excess", offset=0.0, scale=2.0))], dtype=np.float64)
+    assert (own.offset == 0).all() and (own.scale == 2).all() and own.dtype == np.float64 and own.velocity_representation is None
+    assert js.data.RewardSpec.build(icub, terminations=[("fell", dict(term="base_height", below=0.3))]).n_terms == 0
+    build = js.data.RewardSpec.build
+    ok = dict(term="base_height")
+    for rewards, terminations in (
+        ([], []), ("base_height", []), ([("a", ok), ("a", ok)], []), ([("a", ok)], [("a", dict(term="base_height", below=0))]), ([("a", dict(term="nothing"))], []),
+        ([("a", dict())], []), ([("a", dict(term="base_height", inner="cube"))], []), ([("a", dict(term="base_height", outer="log"))], []),
+        ([("a", dict(term="base_height", weight=np.inf))], []), ([("a", dict(term="base_height", weight=1e39))], []), ([("a", dict(term="base_height", scale=np.nan))], []),
+        ([("a", dict(term="base_height", clip=(1.0, 0.0)))], []), ([("a", dict(term="base_height", clip=(0.0, np.nan)))], []), ([("a", dict(term="base_height", clip=3.0))], []),
+        ([("a", dict(term="base_height", sigma=0.0))], []), ([("a", dict(term="base_height", sigma=-1.0))], []), ([("a", dict(term="base_height", gain=2))], []),
+        ([("a", dict(term="base_height", index=1))], []), ([("a", dict(term="joint_positions", joints=["no_such_joint"]))], []),
+        ([("a", dict(term="joint_positions", offset=np.zeros(n + 1)))], []), ([("a", dict(term="base_height", target=("source", dict(name="c", rows=2))))], []),
+        ([("a", dict(term="base_height", target=("source", dict(name="c", rows=2, row=2))))], []), ([("a", dict(term="base_height", target="c"))], []),
+        ([("a", dict(term="base_position", target=("source", dict(name="c", rows=2, row=[0, 1]))))], []),
+        ([("a", dict(term=("source", dict(name="c", rows=2)))), ("b", dict(term=("source", dict(name="c", rows=3))))], []),
+        ([(f"s{k}", dict(term=("source", dict(name=f"s{k}", rows=1)))) for k in range(5)], []), ([(f"t{k}", ok) for k in range(33)], []),
+        ([("a", dict(term="joint_positions", key=None))], []), ([("a",)], []), ([3], []),
+        ([], [("c", dict(term="base_height", kind="finished"))]), ([], [("c", dict(term="base_height", below=1.0, above=0.0))]),
+        ([], [("c", dict(term="base_height", below=np.nan))]), ([], [("c", dict(term="base_height", weight=2.0))]),
+        ([], [("c", dict(term="joint_positions")), ("d", dict(term="joint_velocities"))]),
+        ([(f"t{k}", dict(term="tangential_deformation")) for k in range(1024 // (3 * lay.n_points) + 1)], []),
+    ):  # fmt: skip
+        with pytest.raises(ValueError):
+            build(icub, rewards=rewards, terminations=terminations)
+    for kw in (dict(dtype=np.float16), dict(velocity_representation=7), dict(reward_clip=(1.0, -1.0)), dict(reward_clip=1.0), dict(termination_reward=np.nan)):
+        with pytest.raises(ValueError):
+            build(icub, rewards=[("a", ok)], **kw)
+    # a model whose joints have no finite limits gives no joint-limit excess
+    with pytest.raises(ValueError):
+        build(models("box"), rewards=[("limits", dict(term="joint_positions", inner="excess"))])
+
+
+def test_observation_spec_keeps_its_behaviour_with_the_shared_resolver(models):
+    icub = models("icub")
+    spec = js.data.ObservationSpec.build(icub, ["joint_positions", ("source", dict(name="c", rows=3, take=[2, 0])), "projected_gravity"])
+    n = StateLayout.of(icub).n_joints
+    assert list(spec.slices) == ["joint_positions", "c", "projected_gravity"] and spec.size == n + 5
+    np.testing.assert_array_equal(spec.slots[n : n + 2], [(SRC, 0, 2), (SRC, 0, 0)])
+    with pytest.raises(ValueError, match="unknown observation term"):
+        js.data.ObservationSpec.build(icub, ["nothing"])
+
+
+def test_evaluate_refuses_mismatched_arguments_on_the_host(models):
+    """The state of ``stub_data`` is no device buffer: every refusal comes before the first device call."""
+    icub, cart = models("icub"), models("cartpole")
+    N, T = 6, 2
+    data = stub_data(icub, N, np.float32, tile=T)
+    build = js.data.RewardSpec.build
+    spec = build(icub, rewards=[("h", dict(term="base_height")), ("c", dict(term=("source", dict(name="cent", rows=5)), inner="abs"))],
+                 terminations=[("fell", dict(term="base_height", below=0.3))])  # fmt: skip
+    K = spec.n_terms
+
+    def block(rows=5, cols=N, dtype=np.float32, tile=T):
+        b = runtime.DeviceArray.__new__(runtime.DeviceArray)  # (the metadata of a device array without a buffer)
+        b.rows, b.cols, b.dtype, b.tile, b._ptr = rows, cols, np.dtype(dtype), tile, None
+        return b
+
+    good = dict(sources={"cent": block()}, reward=Foreign((N,), "<f4"), done=Foreign((N,), "|u1"))
+    for bad_spec in (build(cart, rewards=[("h", dict(term="base_height"))]), build(icub, rewards=[("h", dict(term="base_height"))], dtype=np.float64),
+                     js.data.ObservationSpec.build(icub, ["base_height"]), "spec", None):  # fmt: skip
+        with pytest.raises(ValueError):
+            data.evaluate(bad_spec, **good)
+    for sources in (None, {}, {"other": block()}, {"cent": block(), "more": block()}, {"cent": block(rows=6)}, {"cent": block(cols=N + 1)},
+                    {"cent": block(dtype=np.float64)}, {"cent": block(tile=4)}, {"cent": np.zeros((5, N), np.float32)}):  # fmt: skip
+        with pytest.raises(ValueError):
+            data.evaluate(spec, **{**good, "sources": sources})
+    bad_outputs = dict(
+        reward=(Foreign((N + 1,), "<f4"), Foreign((N, 2), "<f4"), Foreign((N,), "<f8"), Foreign((N,), "<i4"), Foreign((N,), "<f4", strides=(8,)),
+                Foreign((N, 1), "<f4", strides=(8, 4)), Foreign((N,), "<f4", ptr=0), np.zeros(N, np.float32), "reward"),
+        done=(Foreign((N + 1,), "|u1"), Foreign((N,), "<i4"), Foreign((N, 1), "|u1"), Foreign((N,), "|u1", ptr=0), np.zeros(N, np.uint8), "done"),
+        fired=(Foreign((N,), "<i4"), Foreign((N,), "|u1"), Foreign((N - 1,), "<u4"), np.zeros(N, np.uint32)),
+        steps=(Foreign((N,), "<u4"), Foreign((N,), "<i8"), Foreign((N + 1,), "<i4"), np.zeros(N, np.int32)),
+        terms=(Foreign((N, K + 1), "<f4"), Foreign((N + 1, K), "<f4"), Foreign((N * K,), "<f4"), Foreign((N, K), "<f8"),
+               Foreign((N, K), "<f4", strides=(4 * (K - 1), 4)), Foreign((N, K), "<f4", strides=(4 * K, 8)), np.zeros((N, K), np.float32)),
+    )  # fmt: skip
+    for name, values in bad_outputs.items():
+        for v in values:
+            with pytest.raises(ValueError):
+                data.evaluate(spec, **{**good, name: v, "max_steps": 5})
+    for max_steps in (0, -1):
+        with pytest.raises(ValueError):
+            data.evaluate(spec, **good, steps=Foreign((N,), "<i4"), max_steps=max_steps)
+    with pytest.raises(ValueError):  # (terms of a spec without reward terms)
+        data.evaluate(build(icub, terminations=[("fell", dict(term="base_height", below=0.3))]), reward=good["reward"], done=good["done"],
+                      terms=Foreign((N, 1), "<f4"))  # fmt: skip
