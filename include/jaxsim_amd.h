@@ -476,6 +476,67 @@ int jxs_env_evaluate(jxs_model* model, const jxs_evaluation* evaluation, const v
                      uint8_t* done, uint32_t* fired, void* terms, int terms_dtype, int64_t terms_ld, int32_t* steps,
                      int max_steps, void* stream);
 
+/* jxs_env_contacts: contact sensors of a legged robot, one launch that turns the link kinematics of jxs_refresh_kinematics
+ *   (`link_transforms` [nL*12][N], `link_velocities` [nL*6][N], tiled) into a tiled record `out_record` [G*8][N] per group of
+ *   points -- foot contact, clearance, slip, air time -- laid out as a source block of jxs_env_observe and jxs_env_evaluate,
+ *   so that contact flags in the observation, a feet-air-time reward, a foot-slip penalty and a "trunk touched the ground"
+ *   termination need no host trip.  The reference's user writes these over `js.contact.in_contact` and
+ *   `js.contact.collidable_point_kinematics` under vmap.
+ *   The sensors are described once per model by an immutable table (jxs_contact_sensors_create): P entries (1 <= P <=
+ *   JXS_CONTACT_MAX_POINTS), entry k = {parent_link[k], L_p[k][3]}, in G groups (1 <= G <= JXS_CONTACT_MAX_GROUPS), `groups`
+ *   [G][2] = {first, count >= 1}, whose ranges are disjoint and cover every entry; a point wanted in two groups is listed
+ *   twice.  Per environment and entry, with [R|t] and (v, w) of its parent link, every operation rounded on its own in the
+ *   model's dtype:
+ *     p  = ((R[:,0] x + R[:,1] y) + R[:,2] z) + t,  pd = v + w x p     (src/jaxsim/api/contact.py:18-45,
+ *                                                                       src/jaxsim/rbda/collidable_points.py:9-65)
+ *     h  = height(p_x, p_y) of the model's own terrain, with the operations of the step kernel: flat `terrain_height`; plane
+ *          terrain_height - (n_x p_x + n_y p_y) * (1 / n_z); height field the bilinear interpolant clamped to the border
+ *          samples (src/jaxsim/terrain/terrain.py:15-238)
+ *     c  = p_z - h; the point is in contact when c <= 0 (src/jaxsim/api/contact.py:92-145); a NaN clearance is no contact
+ *     s  = |pd - (pd . n) n|^2 with n the terrain normal (flat: pd_x^2 + pd_y^2; height field: the central-difference
+ *          normal of src/jaxsim/terrain/terrain.py:40-62, the one place with a reciprocal square root); 0 with NULL
+ *          `link_velocities`
+ *   Group g owns rows 8 g + JXS_CONTACT_* of the record:
+ *     FLAG 1 if any point of the group is in contact, else 0;  COUNT the number of points in contact;
+ *     CLEARANCE m = c_first, then m = c_k < m ? c_k : m in entry order;  SLIP_SQ the largest s_k over the points in
+ *     contact, 0 if none;  AIR_TIME a';  CONTACT_TIME b';  TOUCHDOWN 1 if in contact now and a > 0;  FLIGHT_TIME a if
+ *     touchdown, else 0: the length of the flight that just ended.
+ *   `timers` [G*2][N] (tiled, in/out; a of group g at row 2 g, b at 2 g + 1): an environment whose `reset_mask` byte is
+ *   non-zero takes a = b = 0 first -- the mask is the `done` of jxs_env_evaluate as it is --, then a' = contact ? 0 : a + dt
+ *   and b' = contact ? b + dt : 0.  With NULL `timers` rows 4-7 are 0 and nothing is carried.  The feet-air-time reward
+ *   sum (flight - 0.5) touchdown is two terms of jxs_env_evaluate over source rows: weight * sum FLIGHT_TIME and
+ *   -0.5 weight * sum TOUCHDOWN.
+ *   jxs_contact_sensors_create refuses with JXS_EINVAL: G or P outside their ranges, an empty group, one outside the table
+ *   or overlapping an earlier one, an entry of no group, a parent link outside [0, nL), an L_p that is not finite in the
+ *   model's dtype.  A table may be used with every model of the same layout, link count and dtype.
+ *   jxs_env_contacts writes every word of `out_record` of an environment < N, the padding columns of its last tile as zero,
+ *   and `timers` for environments < N only; the mask and the blocks are never read for padding columns.  Asynchronous on
+ *   `stream`; no allocation, synchronisation, memset or host read (legal inside a stream capture).  JXS_EINVAL: a null
+ *   model, table, link_transforms or out_record, N <= 0, dt negative or not finite, a table of another model layout or
+ *   dtype, a misaligned block.                                                                                          */
+#define JXS_CONTACT_MAX_POINTS 1024
+#define JXS_CONTACT_MAX_GROUPS 32
+#define JXS_CONTACT_ROWS 8
+#define JXS_CONTACT_TIMER_ROWS 2
+enum {
+  JXS_CONTACT_FLAG = 0,
+  JXS_CONTACT_COUNT = 1,
+  JXS_CONTACT_CLEARANCE = 2,
+  JXS_CONTACT_SLIP_SQ = 3,
+  JXS_CONTACT_AIR_TIME = 4,
+  JXS_CONTACT_CONTACT_TIME = 5,
+  JXS_CONTACT_TOUCHDOWN = 6,
+  JXS_CONTACT_FLIGHT_TIME = 7
+};
+typedef struct jxs_contact_sensors jxs_contact_sensors;
+int jxs_contact_sensors_create(jxs_model* model, int G, const int32_t* groups /* [G][2] */, int P,
+                               const int32_t* parent_link /* [P] */, const double* L_p /* [P][3] */,
+                               jxs_contact_sensors** out);
+int jxs_contact_sensors_destroy(jxs_contact_sensors* sensors);
+int jxs_env_contacts(jxs_model* model, const jxs_contact_sensors* sensors, const void* link_transforms,
+                     const void* link_velocities, int N, double dt, const uint8_t* reset_mask, void* timers,
+                     void* out_record, void* stream);
+
 /* RigidContacts only.  A contact-force QP or an impact solve whose result is not finite (fp32 on a numerically
  * singular stance) is DISCARDED -- that environment takes the step without contact forces / without the
  * velocity reset instead of poisoning its state -- where the reference would propagate NaN

@@ -274,6 +274,9 @@ def _declare(lib):
         "jxs_evaluation_create": [vp, C.POINTER(EvaluationDesc), C.POINTER(vp)],
         "jxs_evaluation_destroy": [vp],
         "jxs_env_evaluate": [vp, vp, vp, C.POINTER(vp), C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, C.c_int, C.c_int64, vp, C.c_int, vp],
+        "jxs_contact_sensors_create": [vp, C.c_int, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(vp)],
+        "jxs_contact_sensors_destroy": [vp],
+        "jxs_env_contacts": [vp, vp, vp, vp, C.c_int, C.c_double, vp, vp, vp, vp],
         "jxs_step_repeat": [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp],
         "jxs_step_repeat_timed": [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, C.POINTER(C.c_double)],
         "jxs_refresh_kinematics": [vp, vp, vp, vp, C.c_int, vp],

@@ -24,6 +24,7 @@
 
 #include "../../include/jaxsim_amd.h"
 #include "jxs_env_act.h"
+#include "jxs_env_contact.h"
 #include "jxs_env_evaluate.h"
 #include "jxs_env_observe.h"
 #include "jxs_env_ops.h"
@@ -56,7 +57,10 @@ std::atomic<int> g_knobs{-1}, g_duo_max_blocks{0};
 std::atomic<int> g_observe_envs_per_wave{0};  // JXS_OBSERVE_ENVS_PER_WAVE: 0 = the launcher's own rule (tools/bench_env_observe.py)
 std::atomic<int> g_act_envs_per_wave{0};  // JXS_ACT_ENVS_PER_WAVE: 0 = the launcher's own rule (tools/bench_env_act.py)
 std::atomic<int> g_evaluate_envs_per_wave{0};  // JXS_EVALUATE_ENVS_PER_WAVE: 0 = the launcher's own rule (tools/bench_env_evaluate.py)
+std::atomic<int> g_contact_envs_per_wave{0};  // JXS_CONTACT_ENVS_PER_WAVE: 0 = the launcher's own rule (tools/bench_env_contact.py)
 void load_knobs() {
+  const char* cw = std::getenv("JXS_CONTACT_ENVS_PER_WAVE");
+  g_contact_envs_per_wave.store(cw == nullptr ? 0 : std::atoi(cw));
   const char* ew = std::getenv("JXS_EVALUATE_ENVS_PER_WAVE");
   g_evaluate_envs_per_wave.store(ew == nullptr ? 0 : std::atoi(ew));
   const char* ow = std::getenv("JXS_OBSERVE_ENVS_PER_WAVE");
@@ -209,6 +213,15 @@ struct jxs_evaluation {
   double reward_lo = 0, reward_hi = 0, termination_reward = 0;
   void* table = nullptr;  // device
   size_t targets_at = 0, offset_at = 0, scale_at = 0, terms_at = 0, term_params_at = 0, conds_at = 0, cond_limits_at = 0;  // bytes from `table`
+};
+
+// an immutable contact-sensor table on the device (jxs_contact_sensors_create), in one allocation: per group {first, count},
+// per entry its parent link and L_p in the model's dtype
+struct jxs_contact_sensors {
+  int dtype = JXS_F32;
+  int G = 0, P = 0, n_rows = 0, n_joints = 0, n_links = 0;
+  void* table = nullptr;               // device
+  size_t parent_at = 0, points_at = 0;  // bytes from `table`
 };
 
 struct jxs_model {
@@ -967,6 +980,114 @@ __global__ void __launch_bounds__(256) jxs_env_act_kernel(const T* __restrict__ 
   }
 }
 
+// The contact record out[G * 8][N] (tiled) and the timers [G * 2][N] (tiled, in/out) of every environment from its link
+// transforms and velocities (the law is jxs_env_contact.h: every word is what jxs_contact::sense_env gives for its
+// environment).  The frame of jxs_env_observe_kernel: a wave takes E = 2^env_shift consecutive environments -- whole tiles,
+// E >= T --, and the waves of a workgroup (4, or 2 or 1 where the LDS of 4 would pass 64 KB) share nothing.  The points of an
+// environment are independent, so they get lanes; the entries of the table are taken in chunks of `chunk` points
+// (chunk * E <= 512 items, all of them for the tables of a legged robot):
+//   1. work items i = lane, lane + 64, ... over chunk x E, environment fastest, so that the lanes of a point read neighbouring
+//      columns of a tile.  An item reads the 12 transform and 6 velocity rows of its point's parent link -- 18 independent
+//      loads --, evaluates jxs_contact::point_sample and stores clearance and slip into the wave's LDS [2][chunk * E];
+//   2. work items j over G x E, environment fastest: an item folds the samples of its group that lie in this chunk, from
+//      LDS, in entry order (jxs_contact::fold: the sequential rule of the law, which a NaN and a signed zero make
+//      order-dependent).  A group that ends in this chunk applies the timer rule (jxs_contact::finish) and stores its 8 record
+//      rows and 2 timer rows: the stores of the lanes of a row are contiguous.  A group that goes on keeps its fold in LDS
+//      [3][G * E].
+// Last, the padding columns of the last tile of the record are written as zero.  Only environments below N are read: no
+// padding column of a block, and no byte of the mask beyond N.  The steps of one wave follow each other in program order and
+// LDS serves a wave's accesses in order; the fences keep the compiler from moving them.
+template <typename T>
+struct ContactTable {
+  const int32_t* groups;  // [G][2]
+  const int32_t* parent;  // [P]
+  const T* L_p;           // [P][3]
+  int G, P;
+};
+
+template <typename T>
+__global__ void __launch_bounds__(256) jxs_env_contacts_kernel(const T* __restrict__ link_H, const T* __restrict__ link_V, ContactTable<T> tb,
+                                                               jxs_contact::Terrain<T> tr, int n_links, int N, int tile_shift, int env_shift, int chunk,
+                                                               T dt, const uint8_t* __restrict__ reset_mask, T* __restrict__ timers,
+                                                               T* __restrict__ out) {
+  extern __shared__ __align__(16) unsigned char jxs_contacts_lds[];
+  const int lane = threadIdx.x & 63;
+  const int E = 1 << env_shift, tile = 1 << tile_shift, tmask = tile - 1;
+  const int G = tb.G, P = tb.P;
+  const long long env0 = ((long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) << env_shift;
+  if (env0 >= N) return;  // (wave-uniform)
+  const int n_env = (long long)N - env0 < E ? (int)(N - env0) : E;
+  const int items = chunk << env_shift;
+  T* const clearance = reinterpret_cast<T*>(jxs_contacts_lds) + (size_t)(threadIdx.x >> 6) * (size_t)(2 * items + ((3 * G) << env_shift));
+  T* const slip = clearance + items;
+  T* const kept = slip + items;  // [3][G * E]: count, clearance, slip of a group that spans chunks
+  // word of row `row` of environment env0 + e in a tiled block of `rows` rows (rows * T < 2^30: the host checks)
+  auto word_at = [&](int rows, int row, int e) {
+    const long long env = env0 + e;
+    return (size_t)(env >> tile_shift) * (size_t)(rows << tile_shift) + (size_t)((row << tile_shift) + (int)(env & tmask));
+  };
+  const int rows_H = 12 * n_links, rows_V = 6 * n_links, rows_out = jxs_contact::kRows * G, rows_t = jxs_contact::kTimerRows * G;
+  for (int k0 = 0; k0 < P; k0 += chunk) {
+    const int k1 = k0 + chunk < P ? k0 + chunk : P;
+    for (int i = lane; i < ((k1 - k0) << env_shift); i += 64) {
+      const int e = i & (E - 1), k = k0 + (i >> env_shift);
+      if (e >= n_env) continue;
+      const int l = tb.parent[k];
+      const T L_p[3] = {tb.L_p[3 * k], tb.L_p[3 * k + 1], tb.L_p[3 * k + 2]};
+      const size_t at_H = word_at(rows_H, 12 * l, e);
+      T h[12], v[6] = {T(0), T(0), T(0), T(0), T(0), T(0)};
+#pragma unroll
+      for (int r = 0; r < 12; ++r) h[r] = link_H[at_H + ((size_t)r << tile_shift)];
+      if (link_V != nullptr) {
+        const size_t at_V = word_at(rows_V, 6 * l, e);
+#pragma unroll
+        for (int r = 0; r < 6; ++r) v[r] = link_V[at_V + ((size_t)r << tile_shift)];
+      }
+      const jxs_contact::Sample<T> s = jxs_contact::point_sample(tr, L_p, link_V != nullptr, [&](int r) { return h[r]; }, [&](int r) { return v[r]; });
+      clearance[i] = s.clearance, slip[i] = s.slip_sq;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    for (int j = lane; j < (G << env_shift); j += 64) {
+      const int e = j & (E - 1), g = j >> env_shift;
+      if (e >= n_env) continue;
+      const int first = tb.groups[2 * g], end = first + tb.groups[2 * g + 1];
+      const int lo = first > k0 ? first : k0, hi = end < k1 ? end : k1;
+      if (lo >= hi) continue;
+      jxs_contact::Fold<T> f{T(0), T(0), T(0)};
+      if (lo != first) f = jxs_contact::Fold<T>{kept[j], kept[(G << env_shift) + j], kept[((2 * G) << env_shift) + j]};
+      for (int k = lo; k < hi; ++k) {
+        const int i = ((k - k0) << env_shift) + e;
+        f = jxs_contact::fold(k == first, f, jxs_contact::Sample<T>{clearance[i], slip[i]});
+      }
+      if (hi != end) {
+        kept[j] = f.count, kept[(G << env_shift) + j] = f.clearance, kept[((2 * G) << env_shift) + j] = f.slip_sq;
+        continue;
+      }
+      T a = T(0), b = T(0), rec[jxs_contact::kRows];
+      const size_t at_t = timers != nullptr ? word_at(rows_t, jxs_contact::kTimerRows * g, e) : 0;
+      if (timers != nullptr) a = timers[at_t], b = timers[at_t + tile];
+      const bool reset = reset_mask != nullptr && reset_mask[env0 + e] != 0;
+      jxs_contact::finish(f, timers != nullptr, reset, dt, &a, &b, rec);
+      if (timers != nullptr) timers[at_t] = a, timers[at_t + tile] = b;
+      const size_t at_o = word_at(rows_out, jxs_contact::kRows * g, e);
+#pragma unroll
+      for (int r = 0; r < jxs_contact::kRows; ++r) out[at_o + ((size_t)r << tile_shift)] = rec[r];
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  }
+  // the padding columns of the last tile: env0 + e in [N, whole tiles)
+  const int n_cols = ((n_env + tmask) >> tile_shift) << tile_shift;
+  if (n_cols > n_env)
+    for (int j = lane; j < (rows_out << env_shift); j += 64) {
+      const int e = j & (E - 1), row = j >> env_shift;
+      if (e >= n_env && e < n_cols) out[word_at(rows_out, row, e)] = T(0);
+    }
+}
+
 namespace {
 // ---- the host side of the per-environment operations (jxs_env_*, jxs_observation_*, jxs_action_*): what their entry
 // points share.  Every refusal comes before the launch and names its entry point (`who`).
@@ -1687,6 +1808,97 @@ int jxs_env_act(jxs_model* model, const jxs_action* action, const void* state, c
                            static_cast<const T*>(feed_forward), static_cast<T*>(out_tau), ac.n_joints, ac.n_rows, N, t.tile_shift, env_shift);
       });
     });
+    return launched(who);
+  });
+}
+
+int jxs_contact_sensors_create(jxs_model* model, int G, const int32_t* groups, int P, const int32_t* parent_link, const double* L_p,
+                               jxs_contact_sensors** out) {
+  if (out == nullptr) return fail(JXS_EINVAL, "null out");
+  *out = nullptr;
+  if (model == nullptr) return fail(JXS_EINVAL, "null model");
+  const char* const who = "jxs_contact_sensors_create";
+  return with_typed(model, [&](auto* mt) -> int {
+    using T = typename std::remove_pointer_t<decltype(mt)>::value_type;
+    const auto& KP = mt->pk.P;
+    int bad = -1;
+    const int err = jxs_contact::table_error(G, groups, P, parent_link, L_p, KP.nL, sizeof(T) == 4, &bad);
+    if (err == jxs_contact::kBadSize)
+      return refuse(who, "G = " + std::to_string(G) + ", P = " + std::to_string(P) + " outside [1, " + std::to_string(JXS_CONTACT_MAX_GROUPS) + "], [1, " +
+                             std::to_string(JXS_CONTACT_MAX_POINTS) + "], or a null table");
+    if (err != jxs_contact::kOk) {
+      const std::string at = std::to_string(bad);
+      switch (err) {
+        case jxs_contact::kBadGroup: return refuse(who, "group " + at + ": an empty range, one outside the table or one that overlaps an earlier group's");
+        case jxs_contact::kUncovered: return refuse(who, "entry " + at + " belongs to no group");
+        case jxs_contact::kBadParent: return refuse(who, "entry " + at + ": parent link " + std::to_string(parent_link[bad]) + " outside [0, " + std::to_string(KP.nL) + ")");
+        default: return refuse(who, "entry " + at + ": L_p not finite in the model's dtype");
+      }
+    }
+    auto cs = std::make_unique<jxs_contact_sensors>();
+    cs->dtype = model->dtype, cs->G = G, cs->P = P, cs->n_rows = KP.n_rows, cs->n_joints = KP.n, cs->n_links = KP.nL;
+    cs->parent_at = ((size_t)G * 2 * sizeof(int32_t) + 15) / 16 * 16;
+    cs->points_at = cs->parent_at + ((size_t)P * sizeof(int32_t) + 15) / 16 * 16;
+    std::vector<unsigned char> host(cs->points_at + (size_t)P * 3 * sizeof(T), 0);
+    int32_t* gr = reinterpret_cast<int32_t*>(host.data());
+    int32_t* pa = reinterpret_cast<int32_t*>(host.data() + cs->parent_at);
+    T* pt = reinterpret_cast<T*>(host.data() + cs->points_at);
+    for (int i = 0; i < 2 * G; ++i) gr[i] = groups[i];
+    for (int k = 0; k < P; ++k) pa[k] = parent_link[k];
+    for (int i = 0; i < 3 * P; ++i) pt[i] = static_cast<T>(L_p[i]);
+    if ((cs->table = upload_table(host, "uploading the contact-sensor table")) == nullptr) return JXS_ENODEVICE;
+    *out = cs.release();
+    return JXS_OK;
+  });
+}
+int jxs_contact_sensors_destroy(jxs_contact_sensors* sensors) { return destroy_table(sensors); }
+
+int jxs_env_contacts(jxs_model* model, const jxs_contact_sensors* sensors, const void* link_transforms, const void* link_velocities, int N, double dt,
+                     const uint8_t* reset_mask, void* timers, void* out_record, void* stream) {
+  const char* const who = "jxs_env_contacts";
+  if (model == nullptr || sensors == nullptr || link_transforms == nullptr || out_record == nullptr) return refuse(who, "null argument");
+  if (N <= 0) return refuse(who, "N must be positive");
+  const jxs_contact_sensors& cs = *sensors;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  return with_typed(model, [&](auto* mt) {
+    using T = typename std::remove_pointer_t<decltype(mt)>::value_type;
+    const auto& KP = mt->pk.P;
+    if (!(dt >= 0.0) || !jxs_obs::affine_ok(dt, T(0))) return refuse(who, "dt must be finite in the model's dtype and not negative");
+    if (!table_fits(cs, model->dtype, KP) || cs.n_links != KP.nL) return refuse(who, "the contact-sensor table was created for another model layout or dtype");
+    EnvTile t;
+    if (const int rc = env_tile(who, mt->pk.G, std::max(12 * KP.nL, jxs_contact::kRows * cs.G), t)) return rc;
+    if ((uintptr_t)link_transforms % sizeof(T) != 0 || (uintptr_t)link_velocities % sizeof(T) != 0 || (uintptr_t)timers % sizeof(T) != 0 ||
+        (uintptr_t)out_record % sizeof(T) != 0)
+      return refuse(who, "link_transforms, link_velocities, timers and out_record must be aligned to their element type");
+    // Environments per wave: one tile, whatever N, asked of the shared rule as its `want` (the knob overrides it).  The lanes
+    // of this kernel run over points x environments, so a wave is full with one tile of a legged robot's table and more
+    // environments only add passes: measured (profiles/env_contact.txt), a wave of 8 -- what the rule gives at N = 65 536 --
+    // takes 1.5 x the time of one of 2 or 4 on the humanoid's 40 points, 16 and 32 take 2.8 x
+    const int want = knob(g_contact_envs_per_wave);
+    const int env_shift = jxs_env::env_shift_for(N, t.tile_shift, want > 0 ? want : t.tile);
+    // points per chunk: 512 items (chunk * E) at the most; 2 * chunk * E + 3 * G * E words per wave, and as many waves per
+    // workgroup, out of 4, 2, 1, as fit 64 KB (the worst case, 32 groups of 64 fp64 environments, is 56 KB for one wave)
+    const int chunk = std::max(1, std::min(cs.P, 512 >> env_shift));
+    const size_t per_wave = (size_t)((2 * chunk + 3 * cs.G) << env_shift) * sizeof(T);
+    int waves_per_block = 4;
+    while (waves_per_block > 1 && waves_per_block * per_wave > 64 * 1024) waves_per_block >>= 1;
+    const unsigned char* b = static_cast<const unsigned char*>(cs.table);
+    const ContactTable<T> tb{reinterpret_cast<const int32_t*>(b), reinterpret_cast<const int32_t*>(b + cs.parent_at), reinterpret_cast<const T*>(b + cs.points_at),
+                             cs.G, cs.P};
+    // the terrain is the model's own: its parameters from the host copy of the model block, its samples from the device one
+    jxs_contact::Terrain<T> tr{};
+    tr.kind = KP.hf ? jxs_contact::kTerrainField : KP.flat ? jxs_contact::kTerrainFlat : jxs_contact::kTerrainPlane;
+    tr.height = KP.terrain_h;
+    for (int k = 0; k < 3; ++k) tr.normal[k] = KP.nrm[k];
+    tr.inv_nz = T(1) / KP.nrm[2];
+    tr.nx = KP.hf_nx, tr.ny = KP.hf_ny, tr.x0 = KP.hf_x0, tr.y0 = KP.hf_y0, tr.idx = KP.hf_idx, tr.idy = KP.hf_idy;
+    tr.delta = KP.hf_delta, tr.inv_2delta = KP.hf_inv_2delta;
+    tr.samples = reinterpret_cast<const T*>(mt->mblk + KP.hf_off);
+    // (env_grid counts four waves per workgroup: a workgroup of 4 / f waves needs f times as many)
+    const dim3 grid = env_grid(env_waves(N, env_shift) * (4 / waves_per_block));
+    hipLaunchKernelGGL((jxs_env_contacts_kernel<T>), grid, dim3(64 * waves_per_block), waves_per_block * per_wave, s, static_cast<const T*>(link_transforms),
+                       static_cast<const T*>(link_velocities), tb, tr, KP.nL, N, t.tile_shift, env_shift, chunk, static_cast<T>(dt), reset_mask,
+                       static_cast<T*>(timers), static_cast<T*>(out_record));
     return launched(who);
   });
 }

@@ -91,7 +91,7 @@ JXS_ENV_HD int access_bytes(unsigned long long address_bits, int rows, int tile,
   return word_bytes;
 }
 
-// Environments per wave of jxs_env_observe, jxs_env_act and jxs_env_evaluate (host only), E = 2^shift with T <= E <= max(T, 32), T = 2^tile_shift:
+// Environments per wave of jxs_env_observe, jxs_env_act, jxs_env_evaluate and jxs_env_contacts (host only), E = 2^shift with T <= E <= max(T, 32), T = 2^tile_shift:
 // as many as still leave the chip 8192 waves (256 CUs x 4 SIMDs x 8), so that what a wave reads once (the table, the derived
 // values' prologue) is shared by more environments at large N, while a small batch is spread over as many waves as it has
 // tiles.  `want` > 0 (the launcher's developer knob) asks for at least that many instead, within the same limits.
@@ -101,6 +101,8 @@ JXS_ENV_HD int access_bytes(unsigned long long address_bits, int rows, int tile,
 // environments takes 7.2 .. 7.4 us, one of 2 or 32 about 11 us; at N = 1024 everything up to 8 is one launch interval (3.6 us).
 // The reward and termination flags (jxs_env_evaluate, profiles/env_evaluate.txt): at N = 65 536 about 123 / 70 / 47.7 / 44.7 / 46.0 us
 // with 2 / 4 / 8 / 16 / 32, at N = 1024 18.9 .. 19.2 us up to 8 and 25.6 / 28.3 us with 16 / 32: the same rule, within 7 % of the best.
+// The contact sensors (jxs_env_contacts, profiles/env_contact.txt) give their points lanes, so one tile fills a wave: their launcher passes
+// `want` = T, one tile per wave whatever N (8 per wave take 1.5 x the time of 2 or 4 at N = 65 536, 16 and 32 take 2.8 x).
 inline int env_shift_for(int N, int tile_shift, int want) {
   const int max_shift = tile_shift > 5 ? tile_shift : 5;
   int shift = tile_shift;

@@ -726,6 +726,74 @@ class JaxSimModelData:
         )  # fmt: skip
         return reward, done
 
+    def link_kinematics(self, out=None):
+        """``(link_transforms, link_velocities)`` of ``jxs_refresh_kinematics`` as they are on the device: two tiled
+        ``DeviceArray``s ``[nL*12][batch_size]`` (rows of ``[R|p]`` per link) and ``[nL*6][batch_size]`` (inertial-fixed link
+        velocities), one launch on the current stream, no download -- what ``contact_sensors`` reads.  ``out``: a pair of
+        blocks of these shapes to write into."""
+        from . import specialize
+        from .api.model import _device_model_fast
+
+        st, nL = self._state, self._model_ref.number_of_links()
+        if out is None:
+            out = (runtime.DeviceArray(nL * 12, st.cols, st.dtype, tile=st.tile), runtime.DeviceArray(nL * 6, st.cols, st.dtype, tile=st.tile))
+        if not isinstance(out, (tuple, list)) or len(out) != 2:
+            raise ValueError("out must be None or a pair (link_transforms, link_velocities) of runtime.DeviceArray")
+        H, V = out
+        self._check_block("out[0] (link_transforms)", H, nL * 12)
+        self._check_block("out[1] (link_velocities)", V, nL * 6)
+        dm = _device_model_fast(self._model_ref, self.dtype)
+        specialize.ensure_mode(dm, self._model_ref, specialize.MODE_KIN)  # (first call: cached object, or built when hipcc is there)
+        _lib.check(_lib.load().jxs_refresh_kinematics(dm.handle, C.c_void_p(st.ptr), C.c_void_p(H.ptr), C.c_void_p(V.ptr), st.cols, runtime._sp()),
+                   "jxs_refresh_kinematics")  # fmt: skip
+        return H, V
+
+    def contact_sensors(self, spec: "ContactSensorSpec", *, kinematics=None, timers=None, reset=None, dt=None, out=None) -> runtime.DeviceArray:
+        """The contact record of ``spec``, a tiled ``DeviceArray`` ``[spec.n_rows][batch_size]`` written by one kernel
+        (``jxs_env_contacts``) on the current stream: per group of points the rows ``CONTACT_FIELDS`` -- contact flag, number
+        of points in contact, smallest clearance, largest squared slip speed of the points in contact, air time, contact
+        time, touchdown and the length of the flight that just ended --, what the reference's user derives from
+        ``js.contact.in_contact`` and ``js.contact.collidable_point_kinematics`` under ``vmap``.  The record is a source block
+        of ``observe`` and ``evaluate`` (``spec.source``): no download, no synchronisation.
+
+        ``kinematics``: the pair ``link_kinematics()`` returned for this state (``None``: computed here, one more launch), or
+        the transforms alone, ``(link_transforms, None)``: no slip.  ``timers``: the in/out block of ``spec.new_timers``
+        (``None``: rows 4-7 are zero and nothing is carried).  ``reset``: what ``reset_where`` takes as a mask, the ``done``
+        of ``evaluate`` included: those environments start from zero timers.  ``dt``: the time a call stands for (default:
+        the model's time step).  ``out``: a block to write into.  ``ValueError`` before any launch for a spec of another
+        model or dtype or a mis-shaped block."""
+        from .api.model import _device_model_fast
+
+        self._check_spec(spec, ContactSensorSpec, "spec")
+        st, nL = self._state, self._model_ref.number_of_links()
+        if spec.n_links != nL:
+            raise ValueError(f"spec was built for a model of {spec.n_links} links, not {nL}")
+        if kinematics is None:
+            kinematics = self.link_kinematics()
+        if not isinstance(kinematics, (tuple, list)) or len(kinematics) != 2:
+            raise ValueError("kinematics must be None or the pair (link_transforms, link_velocities) of link_kinematics()")
+        H, V = kinematics
+        self._check_block("kinematics[0] (link_transforms)", H, nL * 12)
+        if V is not None:
+            self._check_block("kinematics[1] (link_velocities)", V, nL * 6)
+        if timers is not None:
+            self._check_block("timers", timers, spec.n_timer_rows)
+        if out is None:
+            out = runtime.DeviceArray(spec.n_rows, st.cols, st.dtype, tile=st.tile)
+        self._check_block("out", out, spec.n_rows)
+        dt = float(self._model_ref.time_step if dt is None else dt)
+        if not (np.isfinite(dt) and dt >= 0.0):
+            raise ValueError(f"dt = {dt} must be finite and not negative")
+        keep, mptr = (None, None) if reset is None else runtime.as_device_mask(reset, st.cols)
+        dm = _device_model_fast(self._model_ref, self.dtype)
+        _lib.check(
+            _lib.load().jxs_env_contacts(dm.handle, spec._table(dm), C.c_void_p(H.ptr), None if V is None else C.c_void_p(V.ptr), st.cols, dt, mptr,
+                                         None if timers is None else C.c_void_p(timers.ptr), C.c_void_p(out.ptr), runtime._sp()),
+            "jxs_env_contacts",
+        )  # fmt: skip
+        del keep
+        return out
+
 
 def random_model_data(
     model,
@@ -1469,3 +1537,124 @@ class RewardSpec(_SpecTable):
 
     def _create(self, dm, handle) -> None:
         _lib.check(_lib.load().jxs_evaluation_create(dm.handle, C.byref(self._desc()), C.byref(handle)), "jxs_evaluation_create")
+
+
+# rows of a group in the record of ``contact_sensors`` (JXS_CONTACT_* of include/jaxsim_amd.h), and the limits of a table
+CONTACT_FIELDS = {"flag": 0, "count": 1, "clearance": 2, "slip_sq": 3, "air_time": 4, "contact_time": 5, "touchdown": 6, "flight_time": 7}
+CONTACT_ROWS, CONTACT_TIMER_ROWS = 8, 2
+CONTACT_MAX_POINTS, CONTACT_MAX_GROUPS = 1024, 32
+
+
+class ContactSensorSpec(_SpecTable):
+    """What ``JaxSimModelData.contact_sensors`` senses for one model: named groups of points on links (the table of
+    ``jxs_contact_sensors_create``).  Built once on the host -- no device is needed --, uploaded at the first
+    ``contact_sensors``, used for every step of a loop.
+
+    ``groups`` ``[G, 2]`` int32 = first, count; ``parent`` ``[P]`` int32, the link of each entry; ``L_p`` ``[P, 3]`` float64, its
+    position in the link frame; ``group_names`` name the groups, group ``g`` owning rows ``8 g + CONTACT_FIELDS[...]`` of the
+    record and rows ``2 g``, ``2 g + 1`` of the timers."""
+
+    def __init__(self, layout: StateLayout, dtype, n_links: int, group_names, groups, parent, L_p, model=None):
+        self.layout = layout
+        self._model = model  # (new_timers asks its device model for the tile)
+        self.dtype = np.dtype(dtype)
+        self.n_links = int(n_links)
+        self.group_names = tuple(group_names)
+        self.groups = np.ascontiguousarray(groups, dtype=np.int32).reshape(-1, 2)
+        self.parent = np.ascontiguousarray(parent, dtype=np.int32)
+        self.L_p = np.ascontiguousarray(L_p, dtype=np.float64).reshape(-1, 3)
+
+    @property
+    def n_groups(self) -> int:
+        return self.groups.shape[0]
+
+    @property
+    def n_rows(self) -> int:
+        return CONTACT_ROWS * self.n_groups
+
+    @property
+    def n_timer_rows(self) -> int:
+        return CONTACT_TIMER_ROWS * self.n_groups
+
+    @staticmethod
+    def build(model, groups, *, dtype=np.float32) -> "ContactSensorSpec":
+        """``groups``: an ordered ``{name: dict(links=[link names])}`` -- the enabled collidable points of those links, in the
+        order of the model -- or ``{name: dict(points=[(link name, xyz), ...])}`` -- explicit points, so that a model without
+        collision shapes can be sensed too.  A point wanted in two groups is listed in both.  ``ValueError`` for an unknown
+        link, an empty group, more than ``CONTACT_MAX_GROUPS`` groups or ``CONTACT_MAX_POINTS`` points, a point that is not
+        finite in ``dtype``."""
+        dt = np.dtype(dtype)
+        if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
+            raise ValueError(f"dtype {dt} is not float32 or float64")
+        if not isinstance(groups, dict) or not groups:
+            raise ValueError("groups must be a non-empty dict {name: dict(links=[...]) or dict(points=[...])}")
+        names = list(model.link_names())
+        kdp = model.kin_dyn_parameters
+        enabled = np.asarray(kdp.indices_of_enabled_collidable_points, dtype=np.int64)
+        body, point = np.asarray(kdp.contact_body)[enabled], np.asarray(kdp.contact_point, dtype=np.float64).reshape(-1, 3)[enabled]
+        table, parent, L_p = [], [], []
+        for name, opts in groups.items():
+            if not isinstance(opts, dict) or set(opts) not in ({"links"}, {"points"}):
+                raise ValueError(f"group {name!r}: expected dict(links=[...]) or dict(points=[...]), not {opts!r}")
+            first = len(parent)
+            if "links" in opts:
+                for link in opts["links"]:
+                    if link not in names:
+                        raise ValueError(f"group {name!r}: unknown link {link!r}")
+                    on = np.flatnonzero(body == names.index(link))
+                    parent += [names.index(link)] * len(on)
+                    L_p += [point[k] for k in on]
+            else:
+                for entry in opts["points"]:
+                    link, xyz = entry
+                    if link not in names:
+                        raise ValueError(f"group {name!r}: unknown link {link!r}")
+                    xyz = np.asarray(xyz, dtype=np.float64)
+                    if xyz.shape != (3,):
+                        raise ValueError(f"group {name!r}: a point of link {link!r} of shape {xyz.shape}, not (3,)")
+                    parent.append(names.index(link))
+                    L_p.append(xyz)
+            if len(parent) == first:
+                raise ValueError(f"group {name!r} is empty: its links have no enabled collidable point")
+            table.append((first, len(parent) - first))
+        if len(table) > CONTACT_MAX_GROUPS or len(parent) > CONTACT_MAX_POINTS:
+            raise ValueError(f"{len(table)} groups of {len(parent)} points: at most {CONTACT_MAX_GROUPS} groups and {CONTACT_MAX_POINTS} points")
+        L_p = np.asarray(L_p, dtype=np.float64).reshape(-1, 3)
+        with np.errstate(over="ignore"):
+            if not (np.isfinite(L_p).all() and np.isfinite(L_p.astype(dt)).all()):
+                raise ValueError(f"a point is not finite in {dt.name}")
+        return ContactSensorSpec(StateLayout.of(model), dt, model.number_of_links(), groups.keys(), table, parent, L_p, model)
+
+    def rows(self, group, field) -> list[int]:
+        """Row numbers of the record: of one group or a list of groups (``None``: all), one field or a list of fields of
+        ``CONTACT_FIELDS``, group-major."""
+        gs = list(self.group_names) if group is None else [group] if isinstance(group, str) else list(group)
+        fs = [field] if isinstance(field, str) else list(field)
+        unknown = [g for g in gs if g not in self.group_names] + [f for f in fs if f not in CONTACT_FIELDS]
+        if unknown:
+            raise ValueError(f"unknown groups or fields {unknown}: groups {list(self.group_names)}, fields {list(CONTACT_FIELDS)}")
+        return [CONTACT_ROWS * self.group_names.index(g) + CONTACT_FIELDS[f] for g in gs for f in fs]
+
+    def source(self, name: str, fields, groups=None):
+        """The term ``("source", dict(name=, rows=, take=))`` of ``ObservationSpec.build`` and ``RewardSpec.build`` that reads
+        ``fields`` of ``groups`` (``None``: all) from the record passed to ``observe`` / ``evaluate`` as ``sources={name: record}``."""
+        return ("source", dict(name=name, rows=self.n_rows, take=self.rows(groups, fields)))
+
+    def new_timers(self, N: int, *, tile: int | None = None) -> runtime.DeviceArray:
+        """A zeroed timer block ``[2 G][N]`` for ``contact_sensors(timers=)``, in the tiling of the spec's model (``tile``:
+        another one)."""
+        if tile is None:
+            if self._model is None:
+                raise ValueError("a spec that was not built from a model needs tile=")
+            tile = runtime.device_model(self._model, self.dtype).layout.tile
+        return runtime.DeviceArray(self.n_timer_rows, int(N), self.dtype, tile=tile, zero=True)
+
+    _destroy = "jxs_contact_sensors_destroy"
+
+    def _create(self, dm, handle) -> None:
+        i32 = C.POINTER(C.c_int32)
+        _lib.check(
+            _lib.load().jxs_contact_sensors_create(dm.handle, self.n_groups, self.groups.ctypes.data_as(i32), len(self.parent), self.parent.ctypes.data_as(i32),
+                                                   self.L_p.ctypes.data_as(C.POINTER(C.c_double)), C.byref(handle)),
+            "jxs_contact_sensors_create",
+        )  # fmt: skip

@@ -240,6 +240,7 @@ def attach(dm, model, mode: int | None = None, *, build: bool = False, require: 
     return done
 
 
+MODE_KIN = 3  # the cached kinematics (jxs_refresh_kinematics): attached on first use by JaxSimModelData.link_kinematics
 MODE_GRAV = 11
 MODE_CENTROIDAL = 14
 MODE_FRAMES = 15
