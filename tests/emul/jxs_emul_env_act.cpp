@@ -1,4 +1,4 @@
-// TEST INFRASTRUCTURE: host harness of the action-to-torque law (jxs_env_act of jaxsim_amd/csrc/jxs_api.hip).  It drives
+// TEST INFRASTRUCTURE: host harness of the action-to-torque law (jxs_env_act of jaxsim_amd/csrc/jxs_env.hip).  It drives
 // jxs_act::torque_word of jaxsim_amd/csrc/jxs_env_act.h -- the function the device kernel calls per word -- over EVERY word
 // of the tiled torque block on the CPU, reading the tiled state and feed-forward blocks through the index functions of
 // jxs_env_ops.h, so that tests/test_env_act_cpu.py can compare it with the NumPy restatement (tests/env_act_ref.py).  The

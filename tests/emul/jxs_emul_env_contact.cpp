@@ -1,4 +1,4 @@
-// TEST INFRASTRUCTURE: host harness of the contact sensors (jxs_env_contacts of jaxsim_amd/csrc/jxs_api.hip).
+// TEST INFRASTRUCTURE: host harness of the contact sensors (jxs_env_contacts of jaxsim_amd/csrc/jxs_env.hip).
 // It drives jxs_contact::sense_env of jaxsim_amd/csrc/jxs_env_contact.h -- the function the device kernel's pieces make up --
 // over EVERY environment on the CPU, reading and writing the tiled blocks through the index functions of jxs_env_ops.h, and
 // writes the padding columns of the record as zero, so that tests/test_env_contact_cpu.py can compare it with the NumPy

@@ -1,4 +1,4 @@
-// TEST INFRASTRUCTURE: host harness of the reward and termination flags (jxs_env_evaluate of jaxsim_amd/csrc/jxs_api.hip).
+// TEST INFRASTRUCTURE: host harness of the reward and termination flags (jxs_env_evaluate of jaxsim_amd/csrc/jxs_env.hip).
 // It drives jxs_eval::evaluate_env of jaxsim_amd/csrc/jxs_env_evaluate.h -- the function the device kernel's pieces make up --
 // over EVERY environment on the CPU, reading the tiled state and source blocks through the index functions of
 // jxs_env_ops.h, so that tests/test_env_evaluate_cpu.py can compare it with the NumPy restatement

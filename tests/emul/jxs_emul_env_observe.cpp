@@ -1,4 +1,4 @@
-// TEST INFRASTRUCTURE: host harness of the policy observation (jxs_env_observe of jaxsim_amd/csrc/jxs_api.hip).  It drives
+// TEST INFRASTRUCTURE: host harness of the policy observation (jxs_env_observe of jaxsim_amd/csrc/jxs_env.hip).  It drives
 // jxs_obs::slot_value of jaxsim_amd/csrc/jxs_env_observe.h -- the function the device kernel's pieces make up -- over EVERY
 // word of the tensor on the CPU, reading the tiled state and source blocks through the index functions of jxs_env_ops.h, so
 // that tests/test_env_observe_cpu.py can compare it with the NumPy restatement (tests/env_observe_ref.py).  Built by

@@ -1,5 +1,5 @@
 // TEST INFRASTRUCTURE: host harness of the per-environment operations (jxs_env_select, jxs_env_copy, jxs_env_flags of
-// jaxsim_amd/csrc/jxs_api.hip).  It drives the index functions of jaxsim_amd/csrc/jxs_env_ops.h -- the ones the device
+// jaxsim_amd/csrc/jxs_env.hip).  It drives the index functions of jaxsim_amd/csrc/jxs_env_ops.h -- the ones the device
 // kernels are loops around -- over EVERY word of a block on the CPU, so that tests/test_env_ops_cpu.py can compare them
 // with the NumPy restatement (tests/env_ops_ref.py) bit for bit.  Built by tests/env_ops_emul.py with g++.
 #include <cstdint>

@@ -1,4 +1,4 @@
-// TEST INFRASTRUCTURE: host harness of the random reset (jxs_env_randomize of jaxsim_amd/csrc/jxs_api.hip).  It drives
+// TEST INFRASTRUCTURE: host harness of the random reset (jxs_env_randomize of jaxsim_amd/csrc/jxs_env.hip).  It drives
 // the functions of jaxsim_amd/csrc/jxs_env_random.h -- the ones the device kernel is a loop around -- over EVERY word of
 // a block on the CPU, so that tests/test_env_random_cpu.py can compare them with the NumPy restatement
 // (tests/env_random_ref.py).  Built by tests/env_random_emul.py with g++.

@@ -15,17 +15,15 @@ import env_act_ref as ref
 import helpers
 import jaxsim_amd.api as js
 import step_bitwise_cases as sbc
+from env_gpu_support import DTYPES, Guarded, InNaN, assert_same_bits, icub_data, upload_flat
 from jaxsim_amd import _lib, runtime
 from jaxsim_amd.runtime import DeviceArray, DeviceMatrix
 from jaxsim_amd.state import StateLayout
 from test_env_act_cpu import bits, check_against_the_restatement, make_case, same_words
-from test_env_observe_gpu import MODELS, InNaN, upload_flat
-from test_env_ops_gpu import Guarded, assert_same_bits
 
 pytestmark = pytest.mark.gpu
 
-DTYPES = (np.float32, np.float64)
-JOINTED = tuple(k for k in MODELS if k != "box")  # humanoid (T = 2, n = 23), quadruped, cartpole (fixed base, large T)
+JOINTED = ("icub", "quadruped_rigid", "cartpole")  # humanoid (T = 2, n = 23), quadruped, cartpole (fixed base, large T)
 
 
 class Table:
@@ -152,12 +150,6 @@ def test_the_widest_action_tensor(models, knobs, width, envs_per_wave):
 
 
 # ---- the Python layer -----------------------------------------------------------------------------------------------
-def icub_data(models, N, dtype, seed=41):
-    model = sbc.build_model("icub", models)
-    blk = helpers.odata_to_block(model, models.random_data("icub", N, seed=seed, dtype=dtype))
-    return model, blk, js.data.JaxSimModelData.from_state_block(model, blk)
-
-
 def icub_spec(model, dtype, width=None):
     names = list(model.joint_names())
     drive = names[3:] + names[:1]  # (a column order that is not the model's)

@@ -15,11 +15,9 @@ import jaxsim_amd as ja
 import jaxsim_amd.api as js
 import oracle
 import step_bitwise_cases as sbc
+from env_gpu_support import Guarded, InNaN, assert_same_bits
 from jaxsim_amd import _lib, runtime
 from jaxsim_amd.runtime import DeviceArray, DeviceMask, DeviceMatrix
-from test_env_evaluate_gpu import Guarded
-from test_env_observe_gpu import InNaN
-from test_env_ops_gpu import GUARD, assert_same_bits  # noqa: F401  (GUARD: the words Guarded puts around a block)
 
 pytestmark = pytest.mark.gpu
 

@@ -13,54 +13,18 @@ import env_evaluate_emul as emul
 import env_evaluate_ref as ref
 import env_observe_ref as oref
 import helpers
-import jaxsim_amd as ja
 import jaxsim_amd.api as js
 import step_bitwise_cases as sbc
+from env_gpu_support import CONTACT, DTYPES, MODELS, Guarded, InNaN, assert_same_bits, icub_data, same_words
 from jaxsim_amd import _lib, runtime
 from jaxsim_amd.runtime import DeviceArray, DeviceIndices, DeviceMask, DeviceMatrix, DeviceWords
 from jaxsim_amd.state import StateLayout
 from test_env_evaluate_cpu import SOURCE_ROWS, check_against_the_restatement, cond_list, make_sources, term_list
 from test_env_observe_cpu import make_block, same_or_both_nan, tiled_sources
-from test_env_observe_gpu import InNaN
-from test_env_ops_gpu import GUARD, assert_same_bits
-from test_env_random_gpu import CONTACT
 
 pytestmark = pytest.mark.gpu
 
-DTYPES = (np.float32, np.float64)
-MODELS = ("icub", "quadruped_rigid", "cartpole", "box")  # humanoid (T = 2), quadruped, fixed base, no joints
 S = oref.STATE_ROW
-
-
-def same_words(got, want, what):
-    """``assert_same_bits`` for words of any size (the done bytes too)."""
-    got, want = np.ascontiguousarray(got), np.ascontiguousarray(want)
-    assert got.dtype == want.dtype and got.shape == want.shape, what
-    differ = got.view(np.uint8) != want.view(np.uint8)
-    assert not differ.any(), f"{what}: {int(differ.sum())} of {differ.size} bytes differ, first at {int(np.argmax(differ))}"
-
-
-class Guarded:
-    """A destination vector of any word size with GUARD words of a pattern on both sides, all inside one allocation (the
-    ``Guarded`` of tests/test_env_ops_gpu.py holds floating-point blocks only)."""
-
-    def __init__(self, flat):
-        self.dtype, self.n = flat.dtype, flat.shape[0]
-        self.pattern = np.full(GUARD * flat.dtype.itemsize, 0xA5, dtype=np.uint8).view(flat.dtype)
-        host = np.concatenate([self.pattern, flat, self.pattern])
-        self.buf = DeviceArray(1, host.shape[0], flat.dtype, tile=1)
-        _lib.check(_lib.load().jxs_memcpy_h2d(C.c_void_p(self.buf.ptr), host.ctypes.data_as(C.c_void_p), host.nbytes, None), "h2d")
-
-    @property
-    def ptr(self):
-        return self.buf.ptr + GUARD * self.dtype.itemsize
-
-    def block(self):
-        """The block, after checking that both guards still hold the pattern."""
-        host = self.buf.to_host_raw().reshape(-1)
-        same_words(host[:GUARD], self.pattern, "words in FRONT of the destination block were written")
-        same_words(host[GUARD + self.n :], self.pattern, "words BEHIND the destination block were written")
-        return host[GUARD : GUARD + self.n]
 
 
 class Table:
@@ -228,12 +192,6 @@ def test_the_kernel_equals_the_harness_and_reads_nothing_beyond_its_blocks(model
 
 
 # ---- the Python layer -----------------------------------------------------------------------------------------------
-def icub_data(models, N, dtype, rep=ja.VelRepr.Mixed, seed=41):
-    model = sbc.build_model("icub", models)
-    blk = helpers.odata_to_block(model, models.random_data("icub", N, seed=seed, dtype=dtype))
-    return model, blk, js.data.JaxSimModelData.from_state_block(model, blk, rep)
-
-
 def table_of(spec) -> ref.Table:
     return ref.Table(spec.slots, spec.offset, spec.scale, spec.targets, spec.terms, spec.term_params, spec.conditions, spec.condition_limits,
                      *spec.reward_clip, spec.termination_reward)  # fmt: skip

@@ -15,33 +15,13 @@ import helpers
 import jaxsim_amd as ja
 import jaxsim_amd.api as js
 import step_bitwise_cases as sbc
+from env_gpu_support import DTYPES, MODELS, Guarded, InNaN, assert_same_bits, icub_data, upload_flat
 from jaxsim_amd import _lib, runtime
 from jaxsim_amd.runtime import DeviceArray, DeviceMatrix
 from jaxsim_amd.state import StateLayout
 from test_env_observe_cpu import SOURCE_ROWS, check_against_the_restatement, make_block, make_sources, same_or_both_nan, tiled_sources
-from test_env_ops_gpu import Guarded, assert_same_bits
 
 pytestmark = pytest.mark.gpu
-
-DTYPES = (np.float32, np.float64)
-MODELS = ("icub", "quadruped_rigid", "cartpole", "box")  # humanoid (T = 2), quadruped, fixed base, no joints
-PAD = 64  # words of NaN in front of and behind a source block
-
-
-def upload_flat(a) -> DeviceArray:
-    out = DeviceArray(1, a.size, a.dtype, tile=1)
-    _lib.check(_lib.load().jxs_memcpy_h2d(C.c_void_p(out.ptr), a.ctypes.data_as(C.c_void_p), a.nbytes, None), "h2d")
-    return out
-
-
-class InNaN:
-    """A read-only block inside one allocation whose words in front of and behind it are NaN."""
-
-    def __init__(self, flat):
-        nan = np.full(PAD, np.nan, dtype=flat.dtype)
-        self.buf = upload_flat(np.concatenate([nan, flat, nan]))
-        self.ptr = self.buf.ptr + PAD * flat.dtype.itemsize
-
 
 class Table:
     """A ``jxs_observation`` of a device model, destroyed with the object."""
@@ -150,12 +130,6 @@ def test_the_kernel_equals_the_harness_and_reads_no_source_beyond_its_storage(mo
 
 
 # ---- the Python layer -----------------------------------------------------------------------------------------------
-def icub_data(models, N, dtype, rep=ja.VelRepr.Mixed, seed=41):
-    model = sbc.build_model("icub", models)
-    blk = helpers.odata_to_block(model, models.random_data("icub", N, seed=seed, dtype=dtype))
-    return model, blk, js.data.JaxSimModelData.from_state_block(model, blk, rep)
-
-
 @pytest.mark.parametrize("dtype", DTYPES, ids=lambda d: np.dtype(d).name)
 def test_observe_equals_the_host_properties(models, dtype):
     N = 5

@@ -11,26 +11,14 @@ import env_ops_ref as ref
 import helpers
 import jaxsim_amd.api as js
 import step_bitwise_cases as sbc
+from env_gpu_support import DTYPES, Guarded, assert_same_bits
 from jaxsim_amd import _lib, runtime
 from jaxsim_amd.runtime import DeviceArray, DeviceIndices, DeviceMask
 from jaxsim_amd.state import StateLayout, tile_block
 
 pytestmark = pytest.mark.gpu
 
-DTYPES = (np.float32, np.float64)
 GRID = [pytest.param(rows, T, N, dt, id=f"r{rows}-T{T}-N{N}-{np.dtype(dt).name}") for rows, T, N in ref.grid() for dt in DTYPES]
-GUARD = 64  # words of pattern in front of and behind a destination block
-
-
-def bits(a):
-    return a.view(ref.bits_dtype(a.dtype))
-
-
-def assert_same_bits(got, want, what=""):
-    got, want = np.asarray(got).reshape(-1), np.asarray(want).reshape(-1)
-    assert got.dtype == want.dtype and got.shape == want.shape, what
-    differ = bits(got) != bits(want)
-    assert not differ.any(), f"{what}: {int(differ.sum())} of {differ.size} words differ, first at {int(np.argmax(differ))}"
 
 
 def upload_raw(flat, rows, N, T) -> DeviceArray:
@@ -85,29 +73,6 @@ def test_env_select_equals_the_restatement_bitwise(rows, T, N, dtype):
 def test_env_select_with_tiles_wider_than_a_wave_or_of_odd_width(rows, T, N, dtype):
     """Tiles of more than 64 columns read the mask per word instead of from one ballot; an odd tile span takes 4-byte accesses."""
     check_select(rows, T, N, dtype)
-
-
-class Guarded:
-    """A destination block with GUARD words of a pattern on both sides, all inside one allocation."""
-
-    def __init__(self, flat):
-        self.dtype, self.n = flat.dtype, flat.shape[0]
-        u = ref.bits_dtype(flat.dtype)
-        self.pattern = np.full(GUARD, 0xA5A5A5A5A5A5A5A5 & np.iinfo(u).max, dtype=u).view(flat.dtype)
-        host = np.concatenate([self.pattern, flat, self.pattern])
-        self.buf = DeviceArray(1, host.shape[0], flat.dtype, tile=1)
-        _lib.check(_lib.load().jxs_memcpy_h2d(C.c_void_p(self.buf.ptr), host.ctypes.data_as(C.c_void_p), host.nbytes, None), "h2d")
-
-    @property
-    def ptr(self):
-        return self.buf.ptr + GUARD * self.dtype.itemsize
-
-    def block(self):
-        """The block, after checking that both guards still hold the pattern."""
-        host = self.buf.to_host_raw().reshape(-1)
-        assert_same_bits(host[:GUARD], self.pattern, "words in FRONT of the destination block were written")
-        assert_same_bits(host[GUARD + self.n :], self.pattern, "words BEHIND the destination block were written")
-        return host[GUARD : GUARD + self.n]
 
 
 def env_copy(src, src_N, src_T, src_idx, dst_ptr, dst_N, dst_T, dst_idx, rows, K, dtype):

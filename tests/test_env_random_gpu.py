@@ -14,24 +14,15 @@ import helpers
 import jaxsim_amd as ja
 import jaxsim_amd.api as js
 import step_bitwise_cases as sbc
+from env_gpu_support import CONTACT, DTYPES, MODELS, Guarded, assert_same_bits, upload_flat
 from jaxsim_amd import _lib, runtime
-from jaxsim_amd.runtime import DeviceArray, DeviceMask
+from jaxsim_amd.runtime import DeviceMask
 from jaxsim_amd.state import StateLayout
-from test_env_ops_gpu import Guarded, assert_same_bits
 from test_env_random_cpu import check_contract
 
 pytestmark = pytest.mark.gpu
 
-DTYPES = (np.float32, np.float64)
-MODELS = ("icub", "quadruped_rigid", "cartpole", "box")  # humanoid (T = 2), quadruped, fixed base, no joints
 SEED, DRAW, FIRST = 0xC0FFEE123456789, 0x1234567800000009, 70000
-CONTACT = dict(base_pos_bounds=((-1, -1, 0.56), (1, 1, 0.68)), base_rpy_bounds=((-0.3, -0.3, -3), (0.3, 0.3, 3)))  # the humanoid on its feet
-
-
-def upload_flat(a) -> DeviceArray:
-    out = DeviceArray(1, a.size, a.dtype, tile=1)
-    _lib.check(_lib.load().jxs_memcpy_h2d(C.c_void_p(out.ptr), a.ctypes.data_as(C.c_void_p), a.nbytes, None), "h2d")
-    return out
 
 
 def masks_of(N):

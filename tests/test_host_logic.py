@@ -527,3 +527,27 @@ def test_bench_dump_outputs_fields_and_fixed_sample(models, tmp_path, monkeypatc
     assert cols == sorted(set(cols))
     for name, a in arrays.items():
         assert np.array_equal(a, ref[name][cols])
+
+
+def test_the_names_of_api_data_are_one_object_wherever_they_are_imported_from():
+    """``jaxsim_amd.api.data``, ``jaxsim_amd.data`` and -- for the specs and their constants -- ``jaxsim_amd.env_specs``
+    hand out the same objects: an ``isinstance`` check of one module accepts what another built."""
+    import ast
+    import pathlib
+
+    import jaxsim_amd.api.data as api_data
+    from jaxsim_amd import env_specs
+
+    tree = ast.parse(pathlib.Path(api_data.__file__).read_text())
+    names = [a.name for node in tree.body if isinstance(node, ast.ImportFrom) for a in node.names]
+    stay = {"JaxSimModelData", "RandomStateDistribution", "random_model_data", "random_model_data_device", "random_state_bounds"}
+    assert stay < set(names) and {"ObservationSpec", "ActionSpec", "RewardSpec", "ContactSensorSpec"} < set(names)
+    for name in names:
+        assert getattr(api_data, name) is getattr(jdata, name), name
+        if name in stay:  # state sampling and the state block itself: not the business of env_specs
+            assert not hasattr(env_specs, name), name
+        else:
+            assert getattr(env_specs, name) is getattr(jdata, name), name
+    # ... and env_specs stands below data: it imports nothing of it
+    imports = [n for n in ast.walk(ast.parse(pathlib.Path(env_specs.__file__).read_text())) if isinstance(n, (ast.Import, ast.ImportFrom))]
+    assert imports and not any("data" in (getattr(n, "module", None) or "").split(".") or any(a.name.split(".")[-1] == "data" for a in n.names) for n in imports)
