@@ -21,6 +21,8 @@ import dataclasses
 
 import numpy as np
 
+import jaxsim_amd as ja
+from jaxsim_amd import robots
 from oracle import VelRepr
 from oracle import refmath as rm
 from oracle import refrigid as rr
@@ -132,3 +134,23 @@ def advance(model, d, t):
     out = dataclasses.replace(d, base_position=d.base_position + t * pd, base_quaternion=qn,
                               joint_positions=d.joint_positions + t * d.joint_velocities)  # fmt: skip
     return out.update_caches(model)
+
+
+# ---- the models of the Coriolis and CRB forward-dynamics tests ------------------------------------------------------------
+TEXTS = {
+    "anymal": lambda: robots.anymal12_urdf(),
+    "icub": lambda: robots.icub23_urdf(),
+    "octopod": lambda: robots.hub_urdf(8, 2, foot_boxes=4, seed=1),  # branching
+    "cartpole": lambda: robots.cartpole_urdf(),  # fixed base, prismatic joint
+    "chain5": lambda: robots.chain_urdf(5, fixed_base=True, seed=1),  # fixed base mounted with a base-link offset
+    "box": lambda: robots.box_urdf(),  # no joints
+    "lumped": lambda: robots.lumped_tree_urdf(5, seed=1),  # base-link offset, rotated frames
+    "chain9f": lambda: robots.chain_urdf(9, fixed_base=False, seed=2),
+}
+_MODELS = {}
+
+
+def model_of(name):
+    if name not in _MODELS:
+        _MODELS[name] = ja.JaxSimModel.build_from_model_description(TEXTS[name]())
+    return _MODELS[name]

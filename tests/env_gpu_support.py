@@ -1,7 +1,7 @@
 """TEST INFRASTRUCTURE: what the GPU tests of the per-environment operations (tests/test_env_*_gpu.py) share -- bitwise
 comparisons, blocks with guard or NaN words around them inside one allocation, the humanoid's state on the device.  No test
 and no fixture lives here.  Two namesakes differ on purpose and stay where they are: ``same_words`` of
-tests/test_env_act_cpu.py takes two NaNs for the same word (the contract of the action law), the one here compares every
+tests/env_cpu_support.py takes two NaNs for the same word (the contract of the action law), the one here compares every
 byte; ``upload_raw`` of tests/test_env_ops_gpu.py fills a tiled block, ``upload_flat`` here a flat one."""
 
 import ctypes as C

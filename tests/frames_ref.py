@@ -16,6 +16,8 @@ Representations are the product's integer codes (0 Inertial, 1 Body, 2 Mixed).
 
 from __future__ import annotations
 
+import dataclasses
+
 import numpy as np
 
 from oracle import VelRepr
@@ -103,3 +105,52 @@ def link_targets(model):
 def frame_targets(model):
     kdp = model.kin_dyn_parameters
     return np.asarray(kdp.frame_body), np.asarray(kdp.frame_transform, np.float64)
+
+
+# ---- a finite difference in time (tests/test_frames_cpu.py, tests/test_frames_gpu.py) ----------------------------------------
+def advance(model, d, I, h):
+    """The state after time h at constant I_nu (s'' = 0; the base moves with constant velocity in representation I)."""
+    W_H_B = d.base_transform.astype(np.float64)
+    nu = d.generalized_velocity(REPS[I]).astype(np.float64)
+    vB, w = nu[:, :3], nu[:, 3:6]
+    R, p = W_H_B[:, :3, :3], W_H_B[:, :3, 3]
+    if I == 0:  # constant W_v_WB: a screw motion, H(t) = expm(t [w]^ ; t v) H(0)
+        X = np.zeros((d.batch_size, 4, 4))
+        X[:, :3, :3] = rm.wedge(w) * h
+        X[:, :3, 3] = vB * h
+        H = np.stack([_expm(x) for x in X]) @ W_H_B
+    elif I == 1:  # constant B_v_WB: H(t) = H(0) expm(t [w]^ ; t v)
+        X = np.zeros((d.batch_size, 4, 4))
+        X[:, :3, :3] = rm.wedge(w) * h
+        X[:, :3, 3] = vB * h
+        H = W_H_B @ np.stack([_expm(x) for x in X])
+    else:  # constant mixed velocity: p(t) = p + t pdot, R(t) = expm(t [w]^) R
+        H = W_H_B.copy()
+        H[:, :3, 3] = p + h * vB
+        H[:, :3, :3] = np.stack([_expm3(x) for x in rm.wedge(w) * h]) @ R
+    q = np.stack([_quat(Rk) for Rk in H[:, :3, :3]])
+    s = d.joint_positions.astype(np.float64) + h * d.joint_velocities.astype(np.float64)
+    W_v = rs.other_representation_to_inertial(nu[:, :6], REPS[I], H, is_force=False)
+    out = dataclasses.replace(d, base_position=H[:, :3, 3].copy(), base_quaternion=q, joint_positions=s,
+                              base_linear_velocity=W_v[:, :3].copy(), base_angular_velocity=W_v[:, 3:].copy())  # fmt: skip
+    return out.update_caches(model)
+
+
+def _expm(X):
+    out, term = np.eye(4), np.eye(4)
+    for k in range(1, 30):
+        term = term @ X / k
+        out = out + term
+    return out
+
+
+def _expm3(X):
+    return _expm(np.pad(X, ((0, 1), (0, 1))))[:3, :3]
+
+
+def _quat(R):
+    w = np.sqrt(max(0.0, 1.0 + R[0, 0] + R[1, 1] + R[2, 2])) / 2.0
+    x = np.copysign(np.sqrt(max(0.0, 1.0 + R[0, 0] - R[1, 1] - R[2, 2])) / 2.0, R[2, 1] - R[1, 2])
+    y = np.copysign(np.sqrt(max(0.0, 1.0 - R[0, 0] + R[1, 1] - R[2, 2])) / 2.0, R[0, 2] - R[2, 0])
+    z = np.copysign(np.sqrt(max(0.0, 1.0 - R[0, 0] - R[1, 1] + R[2, 2])) / 2.0, R[1, 0] - R[0, 1])
+    return np.array([w, x, y, z])

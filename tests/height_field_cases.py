@@ -18,6 +18,7 @@ import numpy as np
 import helpers
 import jaxsim_amd as ja
 import oracle
+import parity_cases as pc
 from oracle import refterrain
 
 X_RANGE, Y_RANGE, SPACING, DELTA = (-0.55, 0.62), (-0.70, 0.45), (0.07, 0.11), 0.004
@@ -25,12 +26,8 @@ SOFT_N, SOFT_SEED = 70, 23    # SoftContacts and Runge-Kutta cases
 RIGID_N, RIGID_SEED = 24, 5   # RigidContacts / RelaxedRigidContacts cases
 SOFT_CASES = [(name, dtype) for name in ("box", "icub") for dtype in (np.float64, np.float32)]
 # (kind, key) -> (model of the zoo, enabled points, contact parameters): the entries of RIGID_CASES / RELAXED_CASES of
-# tests/test_emulation_parity.py and tests/test_gpu_parity.py under the same keys (test_height_field_edges_cpu checks that)
-CONTACT_CASES = {
-    ("rigid", "box4"): ("box", [0, 1, 2, 3], dict(K=1e5)),
-    ("relaxed", "box8"): ("box", list(range(8)), dict(mu=0.5)),
-    ("relaxed", "anymal16"): ("anymal", helpers.ANYMAL_FEET_16, dict(mu=0.5)),
-}
+# tests/parity_cases.py under the same keys
+CONTACT_CASES = {("rigid", "box4"): pc.RIGID_CASES["box4"], ("relaxed", "box8"): pc.RELAXED_CASES["box8"], ("relaxed", "anymal16"): pc.RELAXED_CASES["anymal16"]}
 REGIONS = ("interior", "x<x_lo", "x>x_hi", "y<y_lo", "y>y_hi", "corners")
 
 
@@ -109,8 +106,7 @@ def soft_case(zoo, name, dtype, rk4: bool = False):
     t, g = edge_field()
     base = zoo(name)
     if rk4:
-        # (a softer ground, as every Runge-Kutta parity case of the suite: tests/test_emulation_parity.py _rk4)
-        base = helpers.with_params(base, integrator=ja.IntegratorType.RungeKutta4, contact_params=ja.SoftContactsParams.build(K=2e4, D=60.0, mu=0.6))
+        base = pc.rk4(base)  # (a softer ground, as every Runge-Kutta parity case of the suite)
     d = zoo.random_data(name, SOFT_N, seed=SOFT_SEED, dtype=dtype)
     model = helpers.with_params(base, terrain=t)
     if rk4:

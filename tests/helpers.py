@@ -7,6 +7,7 @@ import dataclasses
 import numpy as np
 
 import jaxsim_amd as ja
+import jaxsim_amd.api as js
 import oracle
 from jaxsim_amd import robots
 from jaxsim_amd import state as st
@@ -146,6 +147,14 @@ def block_to_odata(model, block: np.ndarray, rep=oracle.VelRepr.Mixed) -> oracle
         f["base_angular_velocity"], f["joint_velocities"], f["tangential_deformation"], velocity_representation=rep,
     )  # fmt: skip
     return d.update_caches(model)
+
+
+#: the product's velocity representation of an oracle state's
+REP = {oracle.VelRepr.Inertial: ja.VelRepr.Inertial, oracle.VelRepr.Body: ja.VelRepr.Body, oracle.VelRepr.Mixed: ja.VelRepr.Mixed}
+
+
+def to_gpu(model, d: oracle.OracleData) -> js.data.JaxSimModelData:
+    return js.data.JaxSimModelData.from_state_block(model, odata_to_block(model, d), REP[d.velocity_representation])
 
 
 def rel_err(a: np.ndarray, ref: np.ndarray) -> float:
@@ -294,8 +303,6 @@ def actuation_state(models, name, model, N, seed, dtype):
     assert (s < -0.3).any() and (s > 0.3).any() and (np.abs(s) <= 0.3).any()
     assert (w <= 0.3).any() and ((w > 0.3) & (w <= 0.8)).any() and (w > 0.8).any()
     return d
-
-
 
 
 # ---- fixed-base models with the rigid contact models [round 3] ---------------------------------------

@@ -20,6 +20,7 @@ import helpers
 import jaxsim_amd as ja
 import oracle
 from jaxsim_amd import robots
+from parity_cases import RK4_SOFT  # the softer ground of every Runge-Kutta case of the suite
 from jaxsim_amd import state as st
 from oracle import VelRepr
 from oracle import refmath as rm
@@ -33,7 +34,6 @@ N_BY_MODEL = {"box": 80}
 SINK_LO = {np.dtype(np.float64): -5.0, np.dtype(np.float32): -4.0}
 MU0_SCALE = 0.5  # stands in for mu in the recipe of the frictionless cases
 PLANE = dict(height=0.02, normal=[0.15, -0.1, 1.0])
-RK4_SOFT = dict(K=2e4, D=60.0, mu=0.6)  # the softer ground of every Runge-Kutta case of the suite (test_emulation_parity._rk4)
 
 
 # ---- the classifier ------------------------------------------------------------------------------------------------------

@@ -41,14 +41,12 @@ CASES = {
 
 def build_model(key, zoo):
     import bench
-    import helpers
-    import jaxsim_amd as ja
+    import parity_cases
 
     if key == "quadruped_rigid":
         return bench.build_quadruped_rigid()
     if key == "rk4_chain9f":
-        soft = ja.SoftContactsParams.build(K=2e4, D=60.0, mu=0.6)  # (inside the stability region of explicit RK4)
-        return helpers.with_params(zoo("chain9f"), integrator=ja.IntegratorType.RungeKutta4, contact_params=soft)
+        return parity_cases.rk4(zoo("chain9f"))  # (a softer ground, inside the stability region of explicit RK4)
     return zoo(key)
 
 

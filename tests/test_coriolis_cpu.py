@@ -20,33 +20,17 @@ import query_emul
 import coriolis_ref as cref
 import helpers
 import jaxsim_amd as ja
-from jaxsim_amd import _lib, robots
+from coriolis_ref import TEXTS, model_of
+from jaxsim_amd import _lib
 from jaxsim_amd.api import model as jm
 from oracle import VelRepr
 from oracle import refstep as rs
 
-TEXTS = {
-    "anymal": lambda: robots.anymal12_urdf(),
-    "icub": lambda: robots.icub23_urdf(),
-    "octopod": lambda: robots.hub_urdf(8, 2, foot_boxes=4, seed=1),  # branching
-    "cartpole": lambda: robots.cartpole_urdf(),  # fixed base, prismatic joint
-    "chain5": lambda: robots.chain_urdf(5, fixed_base=True, seed=1),  # fixed base mounted with a base-link offset
-    "box": lambda: robots.box_urdf(),  # no joints
-    "lumped": lambda: robots.lumped_tree_urdf(5, seed=1),  # base-link offset, rotated frames
-    "chain9f": lambda: robots.chain_urdf(9, fixed_base=False, seed=2),
-}
 # fp32: measured relative error of the emulation against the fp64 restatement (seed 3, N = 4) x 3; measured:
 # anymal 6.5e-8, icub 7.2e-8, octopod 1.3e-7, cartpole 1.6e-7, chain5 1.1e-7, box 3.1e-8, lumped 1.5e-7, chain9f 1.2e-7
 FP32_TOL = {"anymal": 2e-7, "icub": 2.2e-7, "octopod": 4e-7, "cartpole": 5e-7, "chain5": 3.3e-7, "box": 1e-7, "lumped": 4.5e-7,
             "chain9f": 3.6e-7}
 REPS = (VelRepr.Inertial, VelRepr.Body, VelRepr.Mixed)
-_MODELS = {}
-
-
-def model_of(name):
-    if name not in _MODELS:
-        _MODELS[name] = ja.JaxSimModel.build_from_model_description(TEXTS[name]())
-    return _MODELS[name]
 
 
 def rel(a, ref):

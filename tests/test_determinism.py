@@ -16,7 +16,8 @@ import pytest
 import helpers
 import jaxsim_amd as ja
 import jaxsim_amd.api as js
-from test_gpu_parity import RELAXED_CASES, RIGID_CASES, _rk4, to_gpu
+from helpers import to_gpu
+from parity_cases import RELAXED_CASES, RIGID_CASES, rk4
 
 pytestmark = pytest.mark.gpu
 
@@ -41,7 +42,7 @@ def _build(models, kind, key):
     if kind == "euler":
         return models(key), key
     if kind == "rk4":
-        return _rk4(models(key)), key
+        return rk4(models(key)), key
     table, make = (RIGID_CASES, helpers.rigid_model) if "rigid" in kind else (RELAXED_CASES, helpers.relaxed_model)
     name, idx, params = table[key]
     model = make(models(name), idx, **params)

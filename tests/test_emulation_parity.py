@@ -11,10 +11,9 @@ import pytest
 import emul_binding as eb
 import helpers
 import oracle
+import parity_cases as pc
 from oracle import VelRepr
-
-REPR_CODE = {VelRepr.Inertial: 0, VelRepr.Body: 1, VelRepr.Mixed: 2}
-ALL = ["box", "sphere", "pendulum", "double_pendulum", "cartpole", "chain5", "chain9f", "anymal", "icub", "icub16"]
+from parity_cases import ALL, OCTOPOD_FEET_4, OCTOPOD_FEET_16, RELAXED_CASES, REPR_CODE, RIGID_CASES, RK4_MODELS, ROW_MODELS, reduced_qp  # noqa: F401
 
 
 @pytest.mark.parametrize("name", ALL)
@@ -248,24 +247,11 @@ def test_plane_terrain_box_slides_downhill(models):
     assert travelled == pytest.approx(0.5 * 9.81 * np.sin(a) * t * t, rel=0.03)
 
 
-# ---- Runge-Kutta 4 (reference: api/integrators.py:91-167) -----------
-RK4_MODELS = ["box", "sphere", "pendulum", "cartpole", "chain9f", "anymal", "icub16"]  # sphere: 50 points -> 64 lanes
-
-
-def _rk4(model):
-    import jaxsim_amd as ja
-
-    # Explicit RK4 leaves its stability region on the zoo's default contact stiffness (K = 1e6,
-    # D = 2000 at dt = 1 ms amplify light links by 1e7 per step, in the reference too), which
-    # would turn a parity check into a chaos check: the RK4 cases use a softer ground.
-    soft = ja.SoftContactsParams.build(K=2e4, D=60.0, mu=0.6)
-    return helpers.with_params(model, integrator=ja.IntegratorType.RungeKutta4, contact_params=soft)
-
-
+# ---- Runge-Kutta 4 (reference: api/integrators.py:91-167; the softer ground: pc.rk4) ----
 @pytest.mark.parametrize("name", RK4_MODELS)
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])
 def test_rk4_step_matches_oracle(models, name, dtype):
-    model = _rk4(models(name))
+    model = pc.rk4(models(name))
     N = 5
     d = models.random_data(name, N, seed=31, dtype=dtype)
     tau, f = helpers.random_inputs(model, N, 32, dtype)
@@ -282,7 +268,7 @@ def test_rk4_step_matches_oracle(models, name, dtype):
 def test_rk4_link_forces_are_held_over_the_stages(models, rep):
     """The external wrenches are converted to inertial once, with the link transforms of the
     initial state (api/model.py:2641-2646), and held while the stages move the links."""
-    model = _rk4(models("chain9f"))
+    model = pc.rk4(models("chain9f"))
     N = 4
     d = models.random_data("chain9f", N, seed=33, rep=rep)
     tau, f = helpers.random_inputs(model, N, 34, np.float64)
@@ -294,7 +280,7 @@ def test_rk4_link_forces_are_held_over_the_stages(models, rep):
 
 def test_rk4_multi_step_rollout(models):
     for name in ("cartpole", "icub16"):
-        model = _rk4(models(name))
+        model = pc.rk4(models(name))
         d = models.random_data(name, 3, seed=35)
         blk = helpers.odata_to_block(model, d)
         for _ in range(10):
@@ -306,7 +292,7 @@ def test_rk4_multi_step_rollout(models):
 def test_rk4_free_fall_known_answer(models):
     """Constant acceleration: RK4 integrates position exactly, p(t) = p0 + v0 t + g t^2 / 2
     (semi-implicit Euler has an O(dt) position error on the same problem)."""
-    model = _rk4(models("box"))
+    model = pc.rk4(models("box"))
     v0 = np.array([0.3, -0.2, 1.0])
     d = oracle.OracleData.build(model, base_position=[0.0, 0.0, 5.0], base_linear_velocity=v0)
     blk = eb.run(model, eb.MODE_STEP, helpers.odata_to_block(model, d), n_steps=50)
@@ -334,7 +320,7 @@ def test_rk4_pendulum_energy_drift_is_fourth_order(models):
         return (T + U)[0]
 
     out = {}
-    for key, model in (("euler", base), ("rk4", _rk4(base))):
+    for key, model in (("euler", base), ("rk4", pc.rk4(base))):
         d = oracle.OracleData.build(model, joint_positions=[1.0])
         blk = helpers.odata_to_block(model, d)
         e0 = energy(model, blk)
@@ -363,25 +349,17 @@ def test_config1_double_pendulum_from_sdf(models):
     np.testing.assert_allclose(helpers.odata_to_block(model, ref), helpers.odata_to_block(models("double_pendulum"), ref_urdf), atol=1e-12)
 
 
-def _icub80():
-    import jaxsim_amd as ja
-    from jaxsim_amd import robots
-
-    return ja.JaxSimModel.build_from_model_description(robots.icub23_urdf(sole_boxes_per_foot=5))  # 80 points on two links
-
-
 @pytest.mark.parametrize("dtype,tol", [(np.float64, 1e-10), (np.float32, 2e-4)])
 def test_rk4_with_more_points_than_lanes(models, dtype, tol):
     """[round 4] RungeKutta4 with several chunks of collidable points (SoftContacts): the points behind the first
     chunk go through memory at every stage, their stage data (rate of the previous stage, weighted sum of the rates)
     sit in the LDS (jxs_core.h contact_chunk).  80 points on a 24-link humanoid: 32 lanes, three chunks.  Against the
     oracle, one step and a short rollout (in place: the deformation rows are read at every stage and written at the last)."""
-    model = _rk4(_icub80())
+    model = pc.rk4(pc.icub80())
     lay = eb.layout(model)
     assert lay.group == 32 and lay.n_points == 80
     N = 6
-    d = oracle.random_model_data(model, batch_size=N, seed=3, dtype=dtype, base_pos_bounds=((-1, -1, 0.56), (1, 1, 0.66)),
-                                 base_rpy_bounds=((-0.3, -0.3, -3), (0.3, 0.3, 3)))  # fmt: skip
+    d = pc.icub80_data(model, N, dtype)
     rng = np.random.default_rng(5)
     d.tangential_deformation[:] = (1e-3 * rng.normal(size=d.tangential_deformation.shape)).astype(dtype)
     tau, f = helpers.random_inputs(model, N, 7, dtype)
@@ -412,9 +390,9 @@ def test_rk4_point_limits(models):
     from jaxsim_amd import robots
 
     mid = ja.JaxSimModel.build_from_model_description(robots.icub23_urdf(sole_boxes_per_foot=3))  # 48 points
-    assert eb.layout(mid).group == 32 and eb.layout(_rk4(mid)).group == 64  # RK4: one lane per point
-    big = _icub80()
-    assert eb.layout(big).n_points > 64 and eb.layout(_rk4(big)).group == 32  # three chunks of 32
+    assert eb.layout(mid).group == 32 and eb.layout(pc.rk4(mid)).group == 64  # RK4: one lane per point
+    big = pc.icub80()
+    assert eb.layout(big).n_points > 64 and eb.layout(pc.rk4(big)).group == 32  # three chunks of 32
     rigid = helpers.with_params(helpers.rigid_model(big, list(range(80)), K=1e4, D=2e2), integrator=ja.IntegratorType.RungeKutta4)
     with pytest.raises(RuntimeError, match="one lane group"):
         eb.layout(rigid)
@@ -422,44 +400,10 @@ def test_rk4_point_limits(models):
         eb.layout(helpers.with_params(models("box"), integrator=7))
 
 
-# ---- RigidContacts (reference: rbda/contacts/rigid.py:176-539) -------
-# The kernel solves the reduced statement of the reference's QP (oracle/refrigid.py REDUCED_QP);
-# against that statement the interior-point iterates are the same up to rounding, so the fp64
-# check is tight.  tests/test_oracle_rigid.py bounds the distance between the two statements.
-RIGID_CASES = {
-    "box4": ("box", [0, 1, 2, 3], dict(K=1e5)),
-    "anymal16": ("anymal", helpers.ANYMAL_FEET_16, dict(K=1e4, D=1e2)),
-    "anymal4": ("anymal", helpers.ANYMAL_FEET_4, dict()),
-    "chain9f6": ("chain9f", [0, 1, 2, 3, 8, 9], dict(K=1e3, mu=0.8)),
-    "serial12f": ("serial12f", list(range(16)), dict(K=1e3, mu=0.8)),  # two links eleven joints apart
-    "icub8": ("icub16", [0, 1, 2, 3, 8, 9, 10, 11], dict(K=1e4)),
-    "planar_biped": ("planar_biped", list(range(16)), dict(K=1e4)),  # [round 5] six parallel joint axes between the two feet
-    "planar10f": ("planar10f", list(range(16)), dict(K=1e3, mu=0.8)),
-    # <= 4 points in a 32-lane group: the row-distributed register solver with the general Delassus sweeps
-    # (two points per foot: no merged sweep)
-    "icub4": ("icub16", [2, 9, 10, 11], dict(K=1e4)),
-    "anymal2": ("anymal", [0, 16], dict()),  # merged sweeps and the 12-row solver with identity padding
-}
-
-
-@pytest.fixture()
-def reduced_qp():
-    from oracle import refrigid
-
-    refrigid.REDUCED_QP = True
-    yield refrigid
-    refrigid.REDUCED_QP = False
-
-
-def _rigid_case(models, key, N, seed, dtype=np.float64):
-    name, idx, params = RIGID_CASES[key]
-    model = helpers.rigid_model(models(name), idx, **params)
-    return model, models.random_data(name, N, seed=seed, dtype=dtype)
-
-
+# ---- RigidContacts (the cases: parity_cases.RIGID_CASES) -------
 @pytest.mark.parametrize("key", list(RIGID_CASES))
 def test_rigid_step_matches_oracle(models, reduced_qp, key):
-    model, d = _rigid_case(models, key, 8, seed=5)
+    model, d = pc.rigid_case(models, key, 8, seed=5)
     tau, f = helpers.random_inputs(model, 8, 7, np.float64)
     ref = oracle.step(model, d, link_forces=f, joint_force_references=tau)
     out = eb.run(model, eb.MODE_STEP, helpers.odata_to_block(model, d), tau=tau.T, link_forces=f.reshape(8, -1).T, force_repr=2)
@@ -473,9 +417,7 @@ def test_rigid_step_matches_oracle(models, reduced_qp, key):
 
 @pytest.mark.parametrize("rep", [VelRepr.Inertial, VelRepr.Body])
 def test_rigid_link_force_representations(models, reduced_qp, rep):
-    name, idx, params = RIGID_CASES["anymal4"]
-    model = helpers.rigid_model(models(name), idx, **params)
-    d = models.random_data(name, 4, seed=9, rep=rep)
+    model, d = pc.rigid_case(models, "anymal4", 4, seed=9, rep=rep)
     tau, f = helpers.random_inputs(model, 4, 10, np.float64)
     ref = oracle.step(model, d, link_forces=f, joint_force_references=tau)
     out = eb.run(model, eb.MODE_STEP, helpers.odata_to_block(model, d), tau=tau.T, link_forces=f.reshape(4, -1).T, force_repr=REPR_CODE[rep])
@@ -485,9 +427,7 @@ def test_rigid_link_force_representations(models, reduced_qp, rep):
 def test_rigid_tight_solver_tolerance_is_statement_independent(models):
     """With solver_tol = 1e-10 the kernel (reduced QP) and the reference's statement of the QP
     converge to the same, unique, minimiser."""
-    name, idx, params = RIGID_CASES["anymal4"]
-    model = helpers.rigid_model(models(name), idx, build=dict(solver_options={"solver_tol": 1e-10}), **params)
-    d = models.random_data(name, 6, seed=5)
+    model, d = pc.rigid_case(models, "anymal4", 6, seed=5, build=dict(solver_options={"solver_tol": 1e-10}))
     ref = oracle.step(model, d)  # reference form (REDUCED_QP off)
     out = eb.run(model, eb.MODE_STEP, helpers.odata_to_block(model, d))
     assert helpers.rel_err(out, helpers.odata_to_block(model, ref)) < 1e-8
@@ -497,7 +437,7 @@ def test_rigid_tight_solver_tolerance_is_statement_independent(models):
 def test_rigid_step_fp32(models, reduced_qp, key, tol):
     """fp32 against the fp64 oracle on the same inputs, well-conditioned contact sets (one point per
     rigid body in contact or a single box)."""
-    model, d = _rigid_case(models, key, 8, seed=5, dtype=np.float32)
+    model, d = pc.rigid_case(models, key, 8, seed=5, dtype=np.float32)
     ref = oracle.step(model, helpers.upcast(d))
     out = eb.run(model, eb.MODE_STEP, helpers.odata_to_block(model, d))
     assert out.dtype == np.float32
@@ -506,9 +446,7 @@ def test_rigid_step_fp32(models, reduced_qp, key, tol):
 
 def test_rigid_tumbling_box_rollout(models, reduced_qp):
     """300 steps of a box dropped on an edge with forward speed: impacts, sliding, rolling."""
-    model = helpers.rigid_model(models("box"), [0, 1, 2, 3], K=1e5)
-    q = oracle.refmath.quaternion_from_euler_xyz(np.array([[0.3, 0.2, 0.1]]))
-    d = oracle.OracleData.build(model, base_position=[0, 0, 0.3], base_quaternion=q, base_linear_velocity=[0.5, 0, 0])
+    model, d = pc.tumbling_box(models, "rigid")
     out = eb.run(model, eb.MODE_STEP, helpers.odata_to_block(model, d), n_steps=300)
     for _ in range(300):
         d = oracle.step(model, d)
@@ -519,38 +457,17 @@ def test_rigid_tumbling_box_rollout(models, reduced_qp):
 @pytest.mark.parametrize("dtype,atol", [(np.float64, 1e-4), (np.float32, 2e-4)])
 def test_rigid_box_settles_known_answer(models, dtype, atol):
     """reference tests/test_simulations.py:245-292: z -> box_height / 2 = 0.05 with no penetration."""
-    model = helpers.rigid_model(models("box"), [0, 1, 2, 3], build=dict(solver_options={"solver_tol": 1e-3}), K=1e5)
+    model = pc.settling_box(models, "rigid")
     d = oracle.OracleData.build(model, base_position=[0.0, 0.0, 0.2], velocity_representation=VelRepr.Inertial)
     out = eb.run(model, eb.MODE_STEP, helpers.odata_to_block(model, d).astype(dtype), n_steps=1000)
     assert abs(out[0, 0]) < 1e-6 and abs(out[1, 0]) < 1e-6
     assert out[2, 0] == pytest.approx(0.05, abs=atol)
 
 
-# ---- RelaxedRigidContacts (SURVEY section 8(f) item 4; reference: rbda/contacts/relaxed_rigid.py) ----
-RELAXED_CASES = {
-    "box4": ("box", [0, 1, 2, 3], dict()),
-    "box8": ("box", list(range(8)), dict(mu=0.5)),
-    "anymal16": ("anymal", helpers.ANYMAL_FEET_16, dict(mu=0.5)),
-    "anymal4": ("anymal", helpers.ANYMAL_FEET_4, dict(time_constant=0.01, damping_coefficient=0.7, power=1.5)),
-    "chain9f6": ("chain9f", [0, 1, 2, 3, 8, 9], dict(mu=0.8, d_min=0.5, d_max=0.99, width=5e-3, midpoint=0.3)),
-    "serial12f": ("serial12f", list(range(16)), dict(mu=0.8, d_min=0.5, d_max=0.99, width=5e-3, midpoint=0.3)),
-    "icub16": ("icub16", list(range(16)), dict(mu=0.5)),
-    # the reference's DEFAULT parameters (mu = 0.005: the regulariser is five orders below the Delassus entries) on two links
-    "icub16d": ("icub16", list(range(16)), dict()),
-    # [round 5] parallel joint axes between the contact links (VERDICT r4 weak #1)
-    "planar_biped": ("planar_biped", list(range(16)), dict(mu=0.5)),
-    "planar10f": ("planar10f", list(range(16)), dict(mu=0.8, d_min=0.5, d_max=0.99, width=5e-3, midpoint=0.3)),
-}
-
-
-def _relaxed_case(models, key, N, seed, dtype=np.float64):
-    name, idx, params = RELAXED_CASES[key]
-    return helpers.relaxed_model(models(name), idx, **params), models.random_data(name, N, seed=seed, dtype=dtype)
-
-
+# ---- RelaxedRigidContacts (the cases: parity_cases.RELAXED_CASES) ----
 @pytest.mark.parametrize("key", list(RELAXED_CASES))
 def test_relaxed_step_matches_oracle(models, key):
-    model, d = _relaxed_case(models, key, 16, seed=5)
+    model, d = pc.relaxed_case(models, key, 16, seed=5)
     tau, f = helpers.random_inputs(model, 16, 7, np.float64)
     ref = oracle.step(model, d, link_forces=f, joint_force_references=tau)
     out = eb.run(model, eb.MODE_STEP, helpers.odata_to_block(model, d), tau=tau.T, link_forces=f.reshape(16, -1).T, force_repr=2)
@@ -583,7 +500,7 @@ def test_relaxed_step_fp32(models, key, tol):
     (condition ~1e6..1e7), the result is noise-limited at 1e-2 .. 1e-1 whatever the solver does -- the fp32
     NumPy restatement is 3e-2 away from fp64 there (HISTORY.md section 4e: use fp64 or the estimated
     parameters, mu = 0.5, with fp32)."""
-    model, d32 = _relaxed_case(models, key, 16, seed=5, dtype=np.float32)
+    model, d32 = pc.relaxed_case(models, key, 16, seed=5, dtype=np.float32)
     tau, f = helpers.random_inputs(model, 16, 7, np.float32)
     blk = helpers.odata_to_block(model, d32)
     d64 = helpers.block_to_odata(model, blk.astype(np.float64), oracle.VelRepr.Mixed)
@@ -607,11 +524,7 @@ def test_standing_on_every_sole_point(models, reduced_qp, kind, name, idx, dtype
     has a singular value at 1e-7 .. 1e-14 of the largest (measured), and whether the impact removes the
     velocity along it is decided by the rcond of the reference's SVD -- a knife edge, not a parity
     statement (HISTORY.md section 4d); in fp32 that direction is below the rounding level altogether."""
-    if kind == "relaxed":
-        model = helpers.relaxed_model(models(name), idx, mu=0.5)
-    else:
-        model = helpers.rigid_model(models(name), idx, K=1e4, D=1e2)
-    d = helpers.standing_data(model, 6, seed=5, dtype=dtype, noise=0.003)
+    model, d = pc.standing_case(models, kind, name, idx, 6, dtype)
     blk = helpers.odata_to_block(model, d)
     d64 = helpers.block_to_odata(model, blk.astype(np.float64), oracle.VelRepr.Mixed)
     from oracle import refrigid
@@ -624,9 +537,7 @@ def test_standing_on_every_sole_point(models, reduced_qp, kind, name, idx, dtype
 
 def test_relaxed_tumbling_box_rollout(models):
     """300 steps of a box dropped on an edge with forward speed."""
-    model = helpers.relaxed_model(models("box"), [0, 1, 2, 3], mu=0.5)
-    q = oracle.refmath.quaternion_from_euler_xyz(np.array([[0.3, 0.2, 0.1]]))
-    d = oracle.OracleData.build(model, base_position=[0, 0, 0.3], base_quaternion=q, base_linear_velocity=[0.5, 0, 0])
+    model, d = pc.tumbling_box(models, "relaxed")
     out = eb.run(model, eb.MODE_STEP, helpers.odata_to_block(model, d), n_steps=300)
     for _ in range(300):
         d = oracle.step(model, d)
@@ -637,7 +548,7 @@ def test_relaxed_tumbling_box_rollout(models):
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])
 def test_relaxed_box_settles_known_answer(models, dtype):
     """reference tests/test_simulations.py:295-346: x, y unchanged (atol 1e-5), z -> 0.05 (atol 1e-4)."""
-    model = helpers.relaxed_model(models("box"), [0, 1, 2, 3], build=dict(solver_options={"tol": 1e-3}))
+    model = pc.settling_box(models, "relaxed")
     d = oracle.OracleData.build(model, base_position=[0.0, 0.0, 0.2], velocity_representation=VelRepr.Inertial)
     out = eb.run(model, eb.MODE_STEP, helpers.odata_to_block(model, d).astype(dtype), n_steps=1000)
     assert abs(out[0, 0]) < 1e-5 and abs(out[1, 0]) < 1e-5
@@ -660,7 +571,7 @@ def test_relaxed_rk4_step_matches_oracle(models, key):
     stage); the reference runs its relaxed-rigid test for every integrator (tests/test_simulations.py:295)."""
     import jaxsim_amd as ja
 
-    model, d = _relaxed_case(models, key, 8, seed=5)
+    model, d = pc.relaxed_case(models, key, 8, seed=5)
     model = helpers.with_params(model, integrator=ja.IntegratorType.RungeKutta4)
     tau, f = helpers.random_inputs(model, 8, 7, np.float64)
     ref = oracle.step(model, d, link_forces=f, joint_force_references=tau)
@@ -675,8 +586,7 @@ def test_relaxed_rk4_box_settles_known_answer(models, dtype):
     """reference tests/test_simulations.py:295-346 with integrator = RungeKutta4."""
     import jaxsim_amd as ja
 
-    model = helpers.relaxed_model(models("box"), [0, 1, 2, 3], build=dict(solver_options={"tol": 1e-3}))
-    model = helpers.with_params(model, integrator=ja.IntegratorType.RungeKutta4)
+    model = pc.settling_box(models, "relaxed", ja.IntegratorType.RungeKutta4)
     d = oracle.OracleData.build(model, base_position=[0.0, 0.0, 0.2], velocity_representation=VelRepr.Inertial)
     out = eb.run(model, eb.MODE_STEP, helpers.odata_to_block(model, d).astype(dtype), n_steps=1000)
     assert abs(out[0, 0]) < 1e-5 and abs(out[1, 0]) < 1e-5
@@ -690,7 +600,7 @@ def test_rigid_rk4_step_matches_oracle(models, reduced_qp, key):
     (tests/test_simulations.py:245)."""
     import jaxsim_amd as ja
 
-    model, d = _rigid_case(models, key, 8, seed=5)
+    model, d = pc.rigid_case(models, key, 8, seed=5)
     model = helpers.with_params(model, integrator=ja.IntegratorType.RungeKutta4)
     tau, f = helpers.random_inputs(model, 8, 7, np.float64)
     ref = oracle.step(model, d, link_forces=f, joint_force_references=tau)
@@ -703,8 +613,7 @@ def test_rigid_rk4_box_settles_known_answer(models, dtype, atol):
     """reference tests/test_simulations.py:245-292 with integrator = RungeKutta4."""
     import jaxsim_amd as ja
 
-    model = helpers.rigid_model(models("box"), [0, 1, 2, 3], build=dict(solver_options={"solver_tol": 1e-3}), K=1e5)
-    model = helpers.with_params(model, integrator=ja.IntegratorType.RungeKutta4)
+    model = pc.settling_box(models, "rigid", ja.IntegratorType.RungeKutta4)
     d = oracle.OracleData.build(model, base_position=[0.0, 0.0, 0.2], velocity_representation=VelRepr.Inertial)
     out = eb.run(model, eb.MODE_STEP, helpers.odata_to_block(model, d).astype(dtype), n_steps=1000)
     assert abs(out[0, 0]) < 1e-6 and abs(out[1, 0]) < 1e-6
@@ -719,7 +628,7 @@ def test_rk4fast_step_matches_oracle(models, reduced_qp, kind, key):
     integrator too (tests/conftest.py:148-152)."""
     import jaxsim_amd as ja
 
-    model, d = (_relaxed_case if kind == "relaxed" else _rigid_case)(models, key, 8, seed=5)
+    model, d = pc.contact_case(models, kind, key, 8, seed=5)
     model = helpers.with_params(model, integrator=ja.IntegratorType.RungeKutta4Fast)
     tau, f = helpers.random_inputs(model, 8, 7, np.float64)
     ref = oracle.step(model, d, link_forces=f, joint_force_references=tau)
@@ -733,8 +642,7 @@ def test_rk4fast_relaxed_box_settles_known_answer(models):
     """reference tests/test_simulations.py:295-346 with integrator = RungeKutta4Fast."""
     import jaxsim_amd as ja
 
-    model = helpers.relaxed_model(models("box"), [0, 1, 2, 3], build=dict(solver_options={"tol": 1e-3}))
-    model = helpers.with_params(model, integrator=ja.IntegratorType.RungeKutta4Fast)
+    model = pc.settling_box(models, "relaxed", ja.IntegratorType.RungeKutta4Fast)
     d = oracle.OracleData.build(model, base_position=[0.0, 0.0, 0.2], velocity_representation=VelRepr.Inertial)
     out = eb.run(model, eb.MODE_STEP, helpers.odata_to_block(model, d), n_steps=1000)
     assert abs(out[0, 0]) < 1e-5 and abs(out[1, 0]) < 1e-5
@@ -749,8 +657,7 @@ def test_rk4fast_rigid_box_rollout_keeps_its_landing_penetration(models, reduced
     the reference's own rigid-contact test passes with this integrator cannot be checked here)."""
     import jaxsim_amd as ja
 
-    model = helpers.rigid_model(models("box"), [0, 1, 2, 3], build=dict(solver_options={"solver_tol": 1e-3}), K=1e5)
-    model = helpers.with_params(model, integrator=ja.IntegratorType.RungeKutta4Fast)
+    model = pc.settling_box(models, "rigid", ja.IntegratorType.RungeKutta4Fast)
     d = oracle.OracleData.build(model, base_position=[0.0, 0.0, 0.06], velocity_representation=VelRepr.Inertial)
     out = eb.run(model, eb.MODE_STEP, helpers.odata_to_block(model, d), n_steps=200)
     for _ in range(200):
@@ -808,10 +715,7 @@ def test_tree_solve_agrees_with_the_dense_path(models, reduced_qp, kind, key, dt
     two links, which is singular between parallel-axis joints: the planar cases here are the ones it got wrong.)"""
     from jaxsim_amd import specialize
 
-    table, make = (RIGID_CASES, helpers.rigid_model) if kind == "rigid" else (RELAXED_CASES, helpers.relaxed_model)
-    name, idx, params = table[key]
-    model = make(models(name), idx, **params)
-    d = models.random_data(name, 16, seed=5, dtype=dtype)
+    model, d = pc.contact_case(models, kind, key, 16, seed=5, dtype=dtype)
     truth = helpers.odata_to_block(model, oracle.step(model, helpers.upcast(d) if dtype == np.float32 else d))
     blk = helpers.odata_to_block(model, d)
     if kind == "rigid":
@@ -832,7 +736,8 @@ def test_tree_solve_agrees_with_the_dense_path(models, reduced_qp, kind, key, dt
         assert "P.ct_tree=0" in specialize.spec(model, np.float32, specialize.MODE_STEP_RIGID)
     if kind == "rigid":
         assert "P.ct_tree=0" in specialize.spec(model, np.float32, specialize.MODE_STEP_RIGID)
-        tight = make(models(name), idx, build=dict(solver_options={"solver_tol": 1e-10}), **params)
+        name, idx, params = RIGID_CASES[key]
+        tight = helpers.rigid_model(models(name), idx, build=dict(solver_options={"solver_tol": 1e-10}), **params)
         assert "P.ct_tree=0" in specialize.spec(tight, np.float64, specialize.MODE_STEP_RIGID)
 
 
@@ -861,16 +766,7 @@ def test_controlled_rollout_equals_the_step_loop(models, name, kind):
     (RungeKutta4, RigidContacts, several chunks: icub80).  Against the oracle stepping with tau[k], and not equal to
     the rollout that holds tau[0]."""
     K, N = 4, 5
-    if name == "icub80":
-        model = _icub80()
-        d = oracle.random_model_data(model, batch_size=N, seed=3, base_pos_bounds=((-1, -1, 0.56), (1, 1, 0.66)), base_rpy_bounds=((-0.3, -0.3, -3), (0.3, 0.3, 3)))
-    else:
-        model = models(name)
-        d = models.random_data(name, N, seed=21)
-    if kind == "rk4":
-        model = _rk4(model)
-    if kind == "rigid":
-        model = helpers.rigid_model(model, helpers.ANYMAL_FEET_4, K=1e4, D=2e2)
+    model, d = pc.rollout_case(models, name, kind, N, seed=21)
     n = model.dofs()
     rng = np.random.default_rng(11)
     tau = rng.uniform(-3, 3, size=(K, N, n))
@@ -893,18 +789,7 @@ def test_recorded_rollout_returns_every_step(models, name, kind, seq):
     steps do not fuse (RungeKutta4, RigidContacts, several point chunks, disabled points).  Every recorded state equals
     the oracle's after that many steps; the last one is the final state."""
     K, N = 4, 5
-    if name == "icub80":
-        model = _icub80()
-        d = oracle.random_model_data(model, batch_size=N, seed=3, base_pos_bounds=((-1, -1, 0.56), (1, 1, 0.66)), base_rpy_bounds=((-0.3, -0.3, -3), (0.3, 0.3, 3)))
-    else:
-        model = models(name)
-        d = models.random_data(name, N, seed=23)
-    if kind == "rk4":
-        model = _rk4(model)
-    if kind == "rigid":
-        model = helpers.rigid_model(model, helpers.ANYMAL_FEET_4, K=1e4, D=2e2)
-    if kind == "disabled":
-        model = helpers.enable_points(model, [0, 1, 2, 3, 8, 9, 10, 11])
+    model, d = pc.rollout_case(models, name, kind, N, seed=23)
     n = model.dofs()
     tau = np.random.default_rng(13).uniform(-3, 3, size=(K, N, n))
     if not seq:
@@ -923,21 +808,12 @@ def test_recorded_rollout_returns_every_step(models, name, kind, seq):
     np.testing.assert_array_equal(plain, final)  # recording does not change the rollout
 
 
-def _quadruped_200():
-    """The quadruped with a 50-point sphere at every shank tip: 200 collidable points, like the real robot's URDF
-    (parsers/rod/utils.py:200-204 turns a sphere collision shape into 50 Fibonacci points)."""
-    import jaxsim_amd as ja
-    from jaxsim_amd import robots
-
-    return ja.JaxSimModel.build_from_model_description(robots.anymal12_urdf(foot_shape="sphere"))
-
-
 @pytest.mark.parametrize("dtype,tol", [(np.float64, 1e-9), (np.float32, 3e-3)])
 def test_relaxed_contacts_with_more_points_than_lanes(dtype, tol):
     """[round 5] RelaxedRigidContacts beyond 64 enabled points (missing #3): 200 points on four links in chunks of
     64 lanes, solved in the tree (jxs_rigid.inc relaxed_contact_forces_chunked) -- random states with a few points down
     and standing states, against the oracle; ten in-place steps stay on the oracle's trajectory."""
-    model = helpers.relaxed_model(_quadruped_200(), range(200), mu=0.5)
+    model = helpers.relaxed_model(pc.quadruped_200(), range(200), mu=0.5)
     assert eb.layout(model, dtype).group == 64  # four chunks of a full wave (measured faster than seven of 32 lanes)
     worst = 0.0
     for d in (oracle.random_model_data(model, batch_size=12, seed=1, dtype=dtype, base_pos_bounds=((-1, -1, 0.55), (1, 1, 0.68)), base_rpy_bounds=((-0.3, -0.3, -3), (0.3, 0.3, 3))),
@@ -963,7 +839,7 @@ def test_chunked_relaxed_solve_equals_the_one_chunk_form(models, n_points, lanes
     """[round 5] The chunked form against the one-lane-per-point form of the SAME problem (a developer knob caps the lane
     group, so that up to 64 points run both ways) and against the oracle: full and partly filled last chunks, a link's
     points split over chunk borders."""
-    base = _quadruped_200() if n_points > 32 else models("anymal")
+    base = pc.quadruped_200() if n_points > 32 else models("anymal")
     model = helpers.relaxed_model(base, range(n_points), mu=0.5)
     d = helpers.standing_data(model, 8, seed=1, noise=0.05)
     blk = helpers.odata_to_block(model, d)
@@ -985,7 +861,7 @@ def test_rigid_contacts_fp64_beyond_47_points_on_three_links(reduced_qp):
     from jaxsim_amd import specialize
 
     idx = list(range(0, 20)) + list(range(50, 70)) + list(range(100, 120))
-    model = helpers.rigid_model(_quadruped_200(), idx, K=1e4, D=2e2)
+    model = helpers.rigid_model(pc.quadruped_200(), idx, K=1e4, D=2e2)
     assert "P.ct_tree=1" in specialize.spec(model, np.float64, specialize.MODE_STEP_RIGID) and eb.layout(model, np.float64).group == 64
     with pytest.raises(RuntimeError, match="does not fit"):
         import os
@@ -1007,7 +883,7 @@ def test_more_points_than_lanes_outside_the_tree_solve_is_refused():
     regulariser (the dense path), Runge-Kutta with a rigid contact model."""
     import jaxsim_amd as ja
 
-    base = _quadruped_200()
+    base = pc.quadruped_200()
     with pytest.raises(RuntimeError, match="at most 64"):
         eb.layout(helpers.rigid_model(base, range(200)), np.float64)
     with pytest.raises(RuntimeError, match="at most 64"):
@@ -1197,9 +1073,6 @@ def test_mass_inverse_kernel_matches_oracle(models, name, dtype, tol):
 
 
 # ---- two-wave workgroups (jxs_core.h: run_inertia + run<MODE_STEP, ROLE_MAIN>) ---------------------------
-ROW_MODELS = ["double_pendulum", "cartpole", "chain5", "anymal", "icub", "icub16"]
-
-
 @pytest.mark.parametrize("name", ROW_MODELS)
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])
 def test_two_wave_step_matches_oracle_and_single_wave(models, name, dtype):
@@ -1253,9 +1126,7 @@ def test_fixed_base_rigid_contacts_match_oracle(reduced_qp, kind, base_velocity)
     base velocity, and its impact writes a base velocity into the state (rbda/contacts/rigid.py:222-446,
     relaxed_rigid.py:330-420, rbda/mass_inverse.py:118-178): reproduced, checked over several steps so that the
     base velocity written by the first impact feeds the next steps."""
-    model = helpers.fixed_cart_model(kind) if kind == "rigid" else helpers.fixed_cart_model(kind, mu=0.5)
-    N = 6
-    d = helpers.fixed_cart_data(model, N, seed=3, base_velocity=base_velocity)
+    model, d = pc.fixed_cart_case(kind, 6, base_velocity)
     p, _ = oracle.collidable_points_pos_vel(model, link_transforms=d.link_transforms, link_velocities=d.link_velocities)
     en = np.flatnonzero(model.kin_dyn_parameters.contact_enabled)
     assert (p[:, en, 2] < 0).any() and (p[:, en, 2] > 0).any()
@@ -1279,11 +1150,8 @@ def test_fifty_point_sphere_matches_oracle(models, reduced_qp, kind, path, monke
     monkeypatch.setenv("JXS_IGNORE_LDS_BUDGET", "1")
     if path == "dense":  # the default is the solve in the tree (jxs_rigid.inc ta_*); the triangles in the LDS stay covered
         monkeypatch.setenv("JXS_DISABLE_CT_TREE", "1")
-    make = helpers.rigid_model if kind == "rigid" else helpers.relaxed_model
-    model = make(models("sphere"), list(range(50)), **(dict(K=1e5) if kind == "rigid" else dict(mu=0.5)))
-    N = 3
-    d = oracle.random_model_data(model, batch_size=N, seed=6, base_pos_bounds=((-1, -1, 0.04), (1, 1, 0.07)),
-                                 base_rpy_bounds=((-3, -3, -3), (3, 3, 3)))  # sunk 3 .. 6 cm: the bottom cap of points touches
+    model = pc.sphere50_model(models, kind)
+    d = pc.sphere50_data(model, 3)
     p, _ = oracle.collidable_points_pos_vel(model, link_transforms=d.link_transforms, link_velocities=d.link_velocities)
     assert (p[..., 2] < 0).sum(axis=1).min() >= 5
     ref = oracle.step(model, d)
@@ -1293,42 +1161,7 @@ def test_fifty_point_sphere_matches_oracle(models, reduced_qp, kind, path, monke
 
 # ---- [round 6] system_dynamics / link_contact_forces (SURVEY section 8(a) rows E and I as callable entries) -----------
 # reference: src/jaxsim/api/ode.py:16-225, src/jaxsim/api/contact.py:514-603; the kernel modes MODE_DYN / MODE_DYN_RIGID
-def _dyn_reference(model, d, tau, f):
-    """(derivative block [rows, N], link contact wrenches [N, nL, 6]) of the oracle for inertial data."""
-    xd = oracle.refstep.system_dynamics(model, d, link_forces=f, joint_torques=tau)
-    blk = helpers.st.pack_state(
-        helpers.st.StateLayout.of(model), base_position=xd["base_position"], base_quaternion=xd["base_quaternion"],
-        joint_positions=xd["joint_positions"], base_linear_velocity=xd["base_linear_velocity"],
-        base_angular_velocity=xd["base_angular_velocity"], joint_velocities=xd["joint_velocities"],
-        tangential_deformation=xd["tangential_deformation"], dtype=np.float64,
-    )  # fmt: skip
-    if oracle.refstep.is_rigid_contact_model(model):
-        from oracle import refrigid
-
-        W_f_L, _ = refrigid.link_contact_forces(model, d, link_forces=f, joint_torques=tau)
-    elif oracle.refstep.is_relaxed_rigid_contact_model(model):
-        from oracle import refrelaxed
-
-        W_f_L, _ = refrelaxed.link_contact_forces(model, d, link_forces=f, joint_torques=tau)
-    elif model.kin_dyn_parameters.number_of_collidable_points() > 0:
-        W_f_L, _ = oracle.refstep.link_contact_forces(model, d)
-    else:
-        W_f_L = np.zeros((d.batch_size, model.number_of_links(), 6))
-    return blk, W_f_L
-
-
-def helpers_dyn_err(a, ref, dtype):
-    """Metric of the derivative / wrench comparisons ([rows, N] blocks).  fp64: helpers.rel_err, element by element.
-    fp32: the worst element error of an environment relative to the LARGEST entry of that environment's reference block
-    (at least 1).  A 1e6 N/m^1.5 contact turns the 6e-8 m an fp32 foot height is known to into a force error of 1e-3 of
-    the contact force, which reaches every acceleration of the tree -- the small ones included; the step's gates see the
-    same error times dt = 1e-3 against states of order one, i.e. the same scale."""
-    if np.dtype(dtype) == np.float64:
-        return helpers.rel_err(a, ref)
-    a, ref = np.asarray(a, np.float64), np.asarray(ref, np.float64)
-    return float(np.max(np.abs(a - ref).max(axis=0) / np.maximum(1.0, np.abs(ref).max(axis=0)))) if a.size else 0.0
-
-
+# (the truth and the error metric: parity_cases.dyn_reference / dyn_err; the blocks here are [rows, N])
 @pytest.mark.parametrize("name", ALL)
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])
 def test_system_dynamics_matches_oracle(models, name, dtype):
@@ -1336,12 +1169,12 @@ def test_system_dynamics_matches_oracle(models, name, dtype):
     N = 32
     d = models.random_data(name, N, seed=4, dtype=dtype, rep=VelRepr.Inertial)
     tau, f = helpers.random_inputs(model, N, 15, dtype)
-    ref_blk, ref_W = _dyn_reference(model, helpers.upcast(d), tau.astype(np.float64), f.astype(np.float64))
+    ref_blk, ref_W = pc.dyn_reference(model, helpers.upcast(d), tau.astype(np.float64), f.astype(np.float64))
     xdot, W = eb.run(model, eb.MODE_DYN, helpers.odata_to_block(model, d), tau=tau.T, link_forces=f.reshape(N, -1).T, force_repr=0)
     assert xdot.dtype == dtype
     tol = helpers.tol_of(dtype, name, evaluation=True)
-    assert helpers_dyn_err(xdot, ref_blk, dtype) < tol
-    assert helpers_dyn_err(W, ref_W.reshape(N, -1).T, dtype) < tol
+    assert pc.dyn_err(xdot, ref_blk, dtype, env_axis=-1) < tol
+    assert pc.dyn_err(W, ref_W.reshape(N, -1).T, dtype, env_axis=-1) < tol
     if name in models.contact_z:
         assert np.abs(ref_W).max() > 1.0  # contacts really act in this sample
 
@@ -1354,17 +1187,17 @@ def test_system_dynamics_takes_the_torques_as_they_are(models):
     d = helpers.actuation_state(models, "anymal", model, N, seed=4, dtype=np.float64)
     d = dataclasses.replace(d, velocity_representation=VelRepr.Inertial)
     tau, f = helpers.random_inputs(model, N, 5, np.float64)
-    ref_blk, _ = _dyn_reference(model, d, tau, None)
+    ref_blk, _ = pc.dyn_reference(model, d, tau, None)
     xdot, _ = eb.run(model, eb.MODE_DYN, helpers.odata_to_block(model, d), tau=tau.T)
     assert helpers.rel_err(xdot, ref_blk) < 1e-10
 
 
 @pytest.mark.parametrize("key", ["box4", "anymal16", "anymal4", "chain9f6", "icub8", "planar_biped"])
 def test_rigid_system_dynamics_matches_oracle(models, reduced_qp, key):
-    model, d = _rigid_case(models, key, 8, seed=5)
+    model, d = pc.rigid_case(models, key, 8, seed=5)
     d = dataclasses.replace(d, velocity_representation=VelRepr.Inertial)
     tau, f = helpers.random_inputs(model, 8, 7, np.float64)
-    ref_blk, ref_W = _dyn_reference(model, d, tau, f)
+    ref_blk, ref_W = pc.dyn_reference(model, d, tau, f)
     xdot, W = eb.run(model, eb.MODE_DYN, helpers.odata_to_block(model, d), tau=tau.T, link_forces=f.reshape(8, -1).T, force_repr=0)
     assert helpers.rel_err(xdot, ref_blk) < 1e-6  # (accelerations: the step's 1e-7 gate is on dt x these)
     assert helpers.rel_err(W.T.reshape(8, -1, 6), ref_W) < 1e-6
@@ -1373,10 +1206,10 @@ def test_rigid_system_dynamics_matches_oracle(models, reduced_qp, key):
 
 @pytest.mark.parametrize("key", ["box8", "anymal16", "chain9f6", "icub16", "planar_biped"])
 def test_relaxed_system_dynamics_matches_oracle(models, key):
-    model, d = _relaxed_case(models, key, 8, seed=5)
+    model, d = pc.relaxed_case(models, key, 8, seed=5)
     d = dataclasses.replace(d, velocity_representation=VelRepr.Inertial)
     tau, f = helpers.random_inputs(model, 8, 7, np.float64)
-    ref_blk, ref_W = _dyn_reference(model, d, tau, f)
+    ref_blk, ref_W = pc.dyn_reference(model, d, tau, f)
     xdot, W = eb.run(model, eb.MODE_DYN, helpers.odata_to_block(model, d), tau=tau.T, link_forces=f.reshape(8, -1).T, force_repr=0)
     assert helpers.rel_err(xdot, ref_blk) < 1e-8
     assert helpers.rel_err(W.T.reshape(8, -1, 6), ref_W) < 1e-8
@@ -1384,22 +1217,11 @@ def test_relaxed_system_dynamics_matches_oracle(models, key):
 
 
 # ---- [round 6] height-field terrain (the generic finite-difference normal, terrain.py:40-62) --
-def _sine_field(extent=4.0, spacing=0.05, amp=0.04):
-    """A rolling terrain: z = amp (sin(2.1 x + 0.3) cos(1.7 y) + 0.3 sin(3.3 y)), sampled on a 5 cm grid over [-extent, extent]^2
-    (slopes up to ~10 degrees: the normal is far from +z).  Returns (product terrain, oracle terrain of the SAME grid)."""
-    import jaxsim_amd as ja
-    from oracle import refterrain
-
-    fn = lambda x, y: amp * (np.sin(2.1 * x + 0.3) * np.cos(1.7 * y) + 0.3 * np.sin(3.3 * y))  # noqa: E731
-    t = ja.HeightFieldTerrain.from_function(fn, x_range=(-extent, extent), y_range=(-extent, extent), spacing=spacing)
-    return t, refterrain.GridTerrain(np.array(t._heights), t._origin, t._spacing, t.delta), fn
-
-
 def test_height_field_host_class_matches_the_restatement():
     """jaxsim_amd.HeightFieldTerrain (product, host) against oracle.refterrain.GridTerrain (independent statement of the
     bilinear interpolant; normal inherited from the reference's Terrain base class), inside, on and outside the grid; and
     against the sampled function itself at the sample points (exact) and between them (interpolation error only)."""
-    t, g, fn = _sine_field(extent=1.0, spacing=0.1)
+    t, g, fn = pc.sine_field(extent=1.0, spacing=0.1)
     rng = np.random.default_rng(0)
     x, y = rng.uniform(-1.4, 1.4, 4000), rng.uniform(-1.4, 1.4, 4000)
     np.testing.assert_allclose(t.height(x, y), g.height(x, y), rtol=0, atol=1e-15)
@@ -1416,7 +1238,7 @@ def test_height_field_host_class_matches_the_restatement():
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])
 @pytest.mark.parametrize("name", ["box", "anymal", "icub"])
 def test_height_field_terrain_soft(models, name, dtype):
-    t, g, _ = _sine_field()
+    t, g, _ = pc.sine_field()
     model = helpers.with_params(models(name), terrain=t)
     N = 12
     d = models.random_data(name, N, seed=23, dtype=dtype)
@@ -1428,16 +1250,16 @@ def test_height_field_terrain_soft(models, name, dtype):
     assert helpers.rel_err(flat, helpers.odata_to_block(model, ref)) > 1e-5  # the terrain really changes the answer
     # and the derivative / link wrenches of system_dynamics see the same terrain
     d_in = dataclasses.replace(helpers.upcast(d, model), velocity_representation=VelRepr.Inertial)
-    ref_blk, ref_W = _dyn_reference(helpers.with_params(model, terrain=g), d_in, None, None)
+    ref_blk, ref_W = pc.dyn_reference(helpers.with_params(model, terrain=g), d_in, None, None)
     xdot, W = eb.run(model, eb.MODE_DYN, helpers.odata_to_block(model, d))
-    assert helpers_dyn_err(xdot, ref_blk, dtype) < max(helpers.tol_of(dtype, name), 1e-3 if dtype == np.float32 else 0)
+    assert pc.dyn_err(xdot, ref_blk, dtype, env_axis=-1) < max(helpers.tol_of(dtype, name), 1e-3 if dtype == np.float32 else 0)
     assert np.abs(ref_W[..., :2]).max() > 0.1  # tilted normals: horizontal contact forces
 
 
 @pytest.mark.parametrize("kind,key", [("rigid", "box4"), ("rigid", "anymal4"), ("relaxed", "box8"), ("relaxed", "anymal16")])
 def test_height_field_terrain_rigid_models(models, reduced_qp, kind, key):
-    t, g, _ = _sine_field()
-    base, d = (_rigid_case if kind == "rigid" else _relaxed_case)(models, key, 24, seed=5)
+    t, g, _ = pc.sine_field()
+    base, d = pc.contact_case(models, kind, key, 24, seed=5)
     model = helpers.with_params(base, terrain=t)
     ref = oracle.step(helpers.with_params(model, terrain=g), d)
     out = eb.run(model, eb.MODE_STEP, helpers.odata_to_block(model, d))
@@ -1473,10 +1295,6 @@ def test_height_field_is_validated(models):
 
 
 # ---- [round 6] links with more than six children (VERDICT r5 missing 3: kMaxChildren 6 -> 12) --------------------------
-OCTOPOD_FEET_4 = [0, 8, 16, 24]                                           # one bottom corner per foot
-OCTOPOD_FEET_16 = [8 * f + c for f in range(4) for c in range(4)]          # the four bottom corners of every foot
-
-
 @pytest.mark.parametrize("name", ["octopod", "hub12"])
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])
 def test_links_with_more_than_six_children(models, name, dtype):
@@ -1524,12 +1342,8 @@ def test_links_with_more_than_six_children(models, name, dtype):
 def test_octopod_with_the_rigid_contact_models(models, reduced_qp, kind, idx):
     """The contact solves on a hub with eight children: the response sweeps, the (merged) Delassus sweeps and the tree
     solve of RelaxedRigidContacts gather children too (jxs_rigid.inc)."""
-    if kind == "rigid":
-        model = helpers.rigid_model(models("octopod"), idx, K=1e4, D=1e2)
-    else:
-        model = helpers.relaxed_model(models("octopod"), idx, mu=0.5)
     N = 8
-    d = models.random_data("octopod", N, seed=5)
+    model, d = pc.octopod_case(models, kind, idx, N)
     tau, f = helpers.random_inputs(model, N, 7, np.float64)
     ref = oracle.step(model, d, link_forces=f, joint_force_references=tau)
     out = eb.run(model, eb.MODE_STEP, helpers.odata_to_block(model, d), tau=tau.T, link_forces=f.reshape(N, -1).T, force_repr=2)

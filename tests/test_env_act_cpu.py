@@ -15,73 +15,14 @@ import pytest
 import env_act_emul as emul
 import env_act_ref as ref
 import jaxsim_amd.api as js
+from env_cpu_support import check_act_against_the_restatement, Foreign, lib, make_action_table, make_case, refused, same_words, stub_data  # noqa: F401  (lib: a fixture)
 from jaxsim_amd import _lib, runtime
 from jaxsim_amd.state import StateLayout
-from test_env_ops_cpu import Foreign, lib, refused, stub_data  # noqa: F401  (lib: a fixture)
 
 DTYPES = (np.float32, np.float64)
 SHAPES = ((23, 32), (12, 4), (2, 0), (1, 3))  # (n_joints, n_points)
 TILES = (1, 2, 4)
 GRID = [pytest.param(n, npt, T, dt, id=f"n{n}-p{npt}-T{T}-{np.dtype(dt).name}") for n, npt in SHAPES for T in TILES for dt in DTYPES]
-SPECIAL = (np.nan, np.inf, -np.inf, -0.0)  # the action words of environments 0 .. 3 of a batch of at least five
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32 if a.dtype == np.float32 else np.uint64)
-
-
-def same_words(got, want, what=""):
-    """Bit for bit; two NaNs are the same word (the module's docstring)."""
-    got, want = np.asarray(got).reshape(-1), np.asarray(want).reshape(-1)
-    assert got.dtype == want.dtype and got.shape == want.shape, what
-    differ = (bits(got) != bits(want)) & ~(np.isnan(got) & np.isnan(want))
-    assert not differ.any(), f"{what}: {int(differ.sum())} of {differ.size} words differ, first at {int(np.argmax(differ))}: {got[differ][:3]} != {want[differ][:3]}"
-
-
-def batch_sizes(T):
-    return sorted({1, T - 1, T + 1, 9 * T + 1} - {0})
-
-
-def make_table(n, A, seed):
-    """A table over n joints and an action tensor of A columns: the four modes in turn, every fifth joint without a column,
-    infinite and finite clips, target windows and torque limits, a clip of zero, an offset of -0; the columns in a shuffled
-    order, and at least one column of a wide enough tensor left unnamed."""
-    rng = np.random.default_rng(1000 + seed)
-    free = list(rng.permutation(A)[: max(A - 1, 1) if A > 1 else A])
-    joints, params = np.zeros((n, 2), np.int32), np.zeros((n, 8))
-    for j in range(n):
-        column = -1 if (j % 5 == 4 or not free) else int(free.pop())
-        joints[j] = ((j + 2) % 4 if n >= 4 else (ref.POSITION, ref.VELOCITY, ref.TORQUE, ref.OFF)[(j + seed) % 4], column)
-        lo, hi = [(-np.inf, np.inf), (rng.uniform(-0.6, -0.1), rng.uniform(0.1, 0.6)), (-np.inf, rng.uniform(0.1, 0.6)), (rng.uniform(-0.6, -0.1), np.inf)][j % 4 if j % 8 < 4 else (j + 1) % 4]
-        params[j] = [rng.uniform(0.25, 2.0) * (-1 if j % 6 == 5 else 1), rng.uniform(-0.5, 0.5), rng.uniform(5, 50), rng.uniform(0.1, 2.0),
-                     np.inf if j % 3 == 0 else rng.uniform(0.3, 1.0), lo, hi, np.inf if j % 7 < 2 else rng.uniform(2, 20)]  # fmt: skip
-    if n >= 12:
-        params[1, ref.OFFSET] = -0.0  # (joint 1 is a torque joint: an action of -0 stays -0)
-        params[1, ref.SCALE] = 1.0
-        params[6, ref.ACTION_CLIP] = 0.0  # clamp(x, -0, 0)
-    return joints, params
-
-
-def make_case(n, n_points, N, dtype, act_dtype, seed, gap=3):
-    """``(block [rows, N], joints, params, actions [N, A + gap], A, feed_forward [n, N])``: NaN in every state row that is
-    neither a joint position nor a joint velocity, in the gap columns and in the columns the table does not name; the action
-    rows 0 .. 3 of a batch of five or more are all NaN, +inf, -inf and -0."""
-    rng = np.random.default_rng(seed)
-    rows = ref.n_rows(n, n_points)
-    A = n + 2
-    joints, params = make_table(n, A, seed)
-    blk = np.full((rows, N), np.nan, dtype)
-    sign = lambda shape: np.where(rng.random(shape) < 0.5, -1.0, 1.0)  # noqa: E731
-    blk[ref.row_q(n) : ref.row_q(n) + n] = (rng.uniform(0.05, 1.5, (n, N)) * sign((n, N))).astype(dtype)
-    blk[ref.row_qd(n) : ref.row_qd(n) + n] = (rng.uniform(0.05, 4.0, (n, N)) * sign((n, N))).astype(dtype)
-    actions = np.full((N, A + gap), np.nan, act_dtype)
-    named = joints[joints[:, 1] >= 0, 1]
-    actions[:, named] = (rng.uniform(0.02, 2.5, (N, len(named))) * sign((N, len(named)))).astype(act_dtype)
-    if N >= 5:
-        for e, v in enumerate(SPECIAL):
-            actions[e, named] = v
-    ff = (rng.uniform(0.1, 3.0, (n, N)) * sign((n, N))).astype(dtype)
-    return blk, joints, params, actions, A, ff
 
 
 def clamp_sides(blk, joints, params, actions, ff):
@@ -110,31 +51,6 @@ def clamp_sides(blk, joints, params, actions, ff):
     return out
 
 
-def check_against_the_restatement(act, n, n_points, T, dtype, what, seed=0, sizes=None):
-    """``act(storage, joints, params, actions, A, N, ff_storage or None) -> flat tiled torque block``, held against the
-    restatement over the batch sizes, float32 and same-dtype actions, with and without feed-forward.  The padding columns
-    of the state and of the feed-forward block hold NaN; those of the result must be +0."""
-    rows = ref.n_rows(n, n_points)
-    for N in sizes or batch_sizes(T):
-        for act_dtype in {np.dtype(np.float32), np.dtype(dtype)}:
-            blk, joints, params, actions, A, ff = make_case(n, n_points, N, dtype, act_dtype, seed + 7 * N)
-            storage = ref.tile_block(blk, T, pad=np.nan)
-            q, qd = blk[ref.row_q(n) : ref.row_q(n) + n], blk[ref.row_qd(n) : ref.row_qd(n) + n]
-            for with_ff in (False, True):
-                tag = f"{what} N={N} actions {act_dtype.name} ff={with_ff}"
-                got = act(storage, joints, params, actions, A, N, ref.tile_block(ff, T, pad=np.nan) if with_ff else None)
-                tau, pad = ref.untile_block(got, n, N, T)
-                assert (bits(pad) == 0).all(), f"{tag}: the padding columns of the torque block are not +0"
-                want = ref.act(q, qd, joints, params, actions, ff if with_ff else None)
-                same_words(tau, want, tag)
-                special = N >= 5 and (joints[:, 1] >= 0).any()
-                assert np.isfinite(tau[:, len(SPECIAL) if N >= 5 else 0 :]).all(), f"{tag}: a NaN from a gap, an unnamed column or a padding column"
-                if special:
-                    driven = joints[:, 1] >= 0
-                    assert np.isnan(tau[driven & (joints[:, 0] != ref.OFF), 0]).all(), f"{tag}: a NaN action must pass through"
-                    assert not np.isnan(tau[~driven, 0]).any()
-
-
 # ---- the harness against the restatement ----------------------------------------------------------------------------
 def emul_act(n, n_points, T):
     def run(storage, joints, params, actions, A, N, ff):
@@ -145,7 +61,7 @@ def emul_act(n, n_points, T):
 
 @pytest.mark.parametrize("n,n_points,T,dtype", GRID)
 def test_the_harness_equals_the_restatement(n, n_points, T, dtype):
-    check_against_the_restatement(emul_act(n, n_points, T), n, n_points, T, dtype, "harness")
+    check_act_against_the_restatement(emul_act(n, n_points, T), n, n_points, T, dtype, "harness")
 
 
 def test_every_clamp_is_met_from_both_sides_and_passed():
@@ -197,7 +113,7 @@ def test_signed_zero_infinities_and_a_hold_entry(dtype):
 
 
 def test_the_validity_check_of_a_table():
-    good_j, good_p = make_table(9, 11, 3)
+    good_j, good_p = make_action_table(9, 11, 3)
     for dt in DTYPES:
         assert ref.table_error(good_j, good_p, 11, dt) == emul.table_error(good_j, good_p, 11, dt) == (ref.OK, -1)
     cases = []  # (joint, change, code); every code at the first, a middle and the last joint

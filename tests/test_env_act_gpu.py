@@ -1,5 +1,5 @@
 """The action-to-torque law on the device: jxs_env_act on guarded raw buffers against the host harness and the NumPy
-restatement, bit for bit (tests/test_env_act_cpu.py: two NaNs are the same word); state and feed-forward inside NaN
+restatement, bit for bit (same_words of tests/env_cpu_support.py: two NaNs are the same word); state and feed-forward inside NaN
 surroundings with NaN padding columns, the action tensor at the end of its upload with NaN in the gap and in unnamed columns;
 waves of several tiles and a tensor of the widest kind; the Python layer (``js.data.ActionSpec`` /
 ``JaxSimModelData.act`` / ``js.model.control_steps``) against the restatement fed from the host properties; the decimation
@@ -15,11 +15,11 @@ import env_act_ref as ref
 import helpers
 import jaxsim_amd.api as js
 import step_bitwise_cases as sbc
+from env_cpu_support import bits, check_act_against_the_restatement, make_case, same_words
 from env_gpu_support import DTYPES, Guarded, InNaN, assert_same_bits, icub_data, upload_flat
 from jaxsim_amd import _lib, runtime
 from jaxsim_amd.runtime import DeviceArray, DeviceMatrix
 from jaxsim_amd.state import StateLayout
-from test_env_act_cpu import bits, check_against_the_restatement, make_case, same_words
 
 pytestmark = pytest.mark.gpu
 
@@ -48,7 +48,7 @@ def env_act(dm, table, state_ptr, act_ptr, act_dtype, act_ld, ff_ptr, out_ptr, N
 
 
 def device_act(dm, n):
-    """The ``act`` of tests/test_env_act_cpu.py::check_against_the_restatement on the device.  The torque block lies in a
+    """The ``act`` of tests/env_cpu_support.py::check_act_against_the_restatement on the device.  The torque block lies in a
     guarded buffer of a known bit pattern; the action tensor ends where its upload ends (a row read at or beyond N would lie
     outside it); state and feed-forward lie between NaN words.  The result is also held against the harness."""
     T = dm.layout.tile
@@ -85,7 +85,7 @@ def test_env_act_equals_the_harness_and_the_restatement(models, key, dtype):
     dm = runtime.device_model(model, dtype)
     lay, T = StateLayout.of(model), dm.layout.tile
     assert (dm.layout.n_rows, dm.layout.n_joints) == (lay.n_rows, lay.n_joints) and ref.n_rows(lay.n_joints, lay.n_points) == lay.n_rows
-    check_against_the_restatement(device_act(dm, lay.n_joints), lay.n_joints, lay.n_points, T, dtype, key, sizes=sizes_of(T, key))
+    check_act_against_the_restatement(device_act(dm, lay.n_joints), lay.n_joints, lay.n_points, T, dtype, key, sizes=sizes_of(T, key))
 
 
 @pytest.mark.parametrize("envs_per_wave", [8, 32])
@@ -97,7 +97,7 @@ def test_waves_of_several_tiles_and_a_partial_last_wave(models, knobs, envs_per_
         model = sbc.build_model(key, models)
         dm = runtime.device_model(model, dtype)
         lay = StateLayout.of(model)
-        check_against_the_restatement(device_act(dm, lay.n_joints), lay.n_joints, lay.n_points, dm.layout.tile, dtype, f"{key} E={envs_per_wave}",
+        check_act_against_the_restatement(device_act(dm, lay.n_joints), lay.n_joints, lay.n_points, dm.layout.tile, dtype, f"{key} E={envs_per_wave}",
                                       seed=11, sizes=(1, dm.layout.tile + 1, 9 * dm.layout.tile + 1))  # fmt: skip
 
 

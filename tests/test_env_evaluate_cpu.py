@@ -14,139 +14,19 @@ import env_evaluate_emul as emul
 import env_evaluate_ref as ref
 import env_observe_ref as oref
 import jaxsim_amd.api as js
+from env_cpu_support import check_evaluate_against_the_restatement, Foreign, GRAV, lib, make_block, make_sources, refused, ROT, S, same_or_both_nan, SRC, stub_data, tiled_sources, VEL  # noqa: F401  (lib: a fixture)
 from jaxsim_amd import _lib, runtime
 from jaxsim_amd.model import VelRepr
 from jaxsim_amd.state import StateLayout
-from test_env_observe_cpu import make_block, same_or_both_nan, tiled_sources
-from test_env_ops_cpu import Foreign, lib, refused, stub_data  # noqa: F401  (lib: a fixture)
 
 DTYPES = (np.float32, np.float64)
 SHAPES = ((23, 32), (12, 4), (2, 0), (1, 3))  # (n_joints, n_points)
 TILES = (1, 2, 4)
-REPRS = (oref.INERTIAL, oref.BODY, oref.MIXED)
-SOURCE_ROWS = (5, 0, 3)  # sources 0 and 2; source 1 does not exist
 GRID = [pytest.param(n, npt, T, dt, id=f"n{n}-p{npt}-T{T}-{np.dtype(dt).name}") for n, npt in SHAPES for T in TILES for dt in DTYPES]
-S, SRC, VEL, GRAV, ROT, QUAT = oref.STATE_ROW, oref.SOURCE_ROW, oref.BASE_VELOCITY, oref.PROJECTED_GRAVITY, oref.BASE_ROTATION, oref.BASE_QUAT_UNIT
-
-
-def batch_sizes(T):
-    return sorted({1, T - 1, T + 1, 9 * T + 1} - {0})
-
-
-def make_sources(N, dtype, seed):
-    rng = np.random.default_rng(seed + 1)
-    return [None if r == 0 else rng.uniform(-3.0, 3.0, size=(r, N)).astype(dtype) for r in SOURCE_ROWS]
-
-
-def term_list(n, seed):
-    """Every inner, both outers, targets, finite and infinite clips, a one-slot term and an n-slot term (23 for the humanoid)."""
-    rng = np.random.default_rng(seed)
-    q, qd = [(S, 0, 7 + j) for j in range(n)], [(S, 0, 13 + n + j) for j in range(n)]
-    terms = [
-        dict(slots=q, inner=ref.EXCESS, offset=rng.uniform(-0.3, 0.3, n), scale=rng.uniform(1.5, 3.0, n), weight=-2.0),
-        dict(slots=qd, inner=ref.SQUARE, weight=-0.01, lo=-0.5),
-        dict(slots=[(S, 0, 2)], offset=0.5, weight=1.5),
-        dict(slots=[(SRC, 0, k) for k in range(3)], inner=ref.ABS, target=[(2, k) for k in range(3)], hi=2.0, weight=0.7),
-        dict(slots=[(VEL, 0, k) for k in range(3)], inner=ref.SQUARE, outer=ref.OUTER_EXP, target=[(0, k) for k in range(3)], scale=0.5),
-        dict(slots=qd[:2], inner=ref.SQUARE, outer=ref.OUTER_EXP, scale=0.3, weight=0.5, offset=0.1),
-        dict(slots=[(GRAV, 0, 0), (GRAV, 0, 1)], inner=ref.SQUARE, weight=-1.0),
-        dict(slots=[(ROT, 0, 8)], weight=0.25, lo=-0.1, hi=0.2),
-        dict(slots=[(QUAT, 0, 0)], inner=ref.ABS, scale=2.0),
-        dict(slots=[(VEL, 0, k) for k in range(3, 6)], inner=ref.ABS, lo=-1.0, hi=1.0, weight=0.1),
-        dict(slots=[(SRC, 2, 1), (S, 0, 0)], inner=ref.IDENTITY, outer=ref.OUTER_EXP, scale=0.2, weight=-0.3),
-    ]
-    return [t for t in terms if len(t["slots"])]  # (a model without joints has no joint terms)
-
-
-def gap_threshold(values, bound):
-    """A threshold in the widest gap of the finite ``values``, and the distance from it to the nearest of them over ``bound``."""
-    v = np.sort(values[np.isfinite(values)])
-    if len(v) < 2:
-        return (float(v[0]) + 1.0 if len(v) else 0.0), np.inf
-    k = int(np.argmax(np.diff(v)))
-    return float((v[k] + v[k + 1]) / 2), float((v[k + 1] - v[k]) / 2 / max(bound, 1e-300))
-
-
-def cond_list(n, blk, srcs, repr_):
-    """Windows on exact kinds, and thresholds on derived kinds placed in the widest gap of the batch's float64 values."""
-    conds = [
-        dict(slot=(S, 0, 2), lo=-0.5, hi=0.8),
-        dict(slot=(SRC, 2, 1), hi=2.0, kind=ref.KIND_TRUNCATED),
-        dict(slot=(S, 0, 7 if n else 1), offset=0.1, scale=1.7, lo=-1.0, hi=1.0),
-        dict(slot=(SRC, 0, 4), target=(2, 0), lo=-2.5, kind=ref.KIND_TRUNCATED),
-    ]
-    probe = ref.make_table(conds=[dict(slot=(GRAV, 0, 2)), dict(slot=(VEL, 0, 0), scale=0.5), dict(slot=(ROT, 0, 0), offset=0.25)])
-    y = ref.slot_words(blk, probe, n, repr_, srcs, dtype=np.float64)
-    b = ref.slot_bounds(blk, probe, n, repr_, srcs)
-    margins = []
-    for k, (slot, extra) in enumerate((((GRAV, 0, 2), {}), ((VEL, 0, 0), dict(scale=0.5)), ((ROT, 0, 0), dict(offset=0.25)))):
-        th, margin = gap_threshold(y[k], float(b[k][np.isfinite(b[k])].max(initial=0.0)))
-        margins.append(margin)
-        conds.append(dict(slot=slot, **extra, **({"hi": th} if k != 1 else {"lo": th}), kind=ref.KIND_TRUNCATED if k == 2 else ref.KIND_TERMINATED))
-    return conds, margins
 
 
 def emul_evaluate(storage, tb, rows, n, N, T, repr_, tsrcs, **kw):
     return emul.evaluate(storage, tb, rows, n, N, T, repr_, sources=tsrcs, **kw)
-
-
-def check_against_the_restatement(evaluate, n, n_points, T, dtype, what, sizes=None, seed=0):
-    """``evaluate(storage, table, rows, n, N, T, repr, tiled sources, steps=, max_steps=, fill=)`` -> dict of outputs against
-    tests/env_evaluate_ref.py over the batch sizes and the three representations.  Returns the worst ratios."""
-    rows = oref.n_rows(n, n_points)
-    eps = float(np.finfo(dtype).eps)
-    worst = {"exp": 0.0, "derived": 0.0, "reward": 0.0}
-    for N in sizes or batch_sizes(T):
-        blk = make_block(n, n_points, N, dtype, seed=seed + 100 * N + rows)
-        srcs = make_sources(N, dtype, seed=N)
-        storage, tsrcs = oref.tile_block(blk, T, pad=np.nan), tiled_sources(srcs, T)
-        steps = np.random.default_rng(N).integers(0, 9, size=N).astype(np.int32)
-        for repr_ in REPRS:
-            tag = f"{what} N={N} repr={repr_}"
-            terms = term_list(n, seed=rows)
-            conds, margins = cond_list(n, blk, srcs, repr_)
-            # (the thresholds on derived kinds are clear of every environment's value by more than its bound: asserted for all)
-            assert min(margins) > 1.0, f"{tag}: a derived threshold lies within the bound of some environment: {margins}"
-            tb = ref.make_table(terms, conds, reward_clip=(-3.0, 2.5), termination_reward=-1.25)
-            exact, is_exp, is_derived = ref.term_classes(tb, repr_)
-            want = ref.evaluate(blk, tb, n, repr_, srcs, steps=steps, max_steps=7)
-            got = evaluate(storage, tb, rows, n, N, T, repr_, tsrcs, steps=steps, max_steps=7)
-            for k in ("done", "fired", "steps"):
-                assert np.array_equal(got[k], want[k]), f"{tag}: {k} {got[k]} != {want[k]}"
-            same_or_both_nan(got["terms"], want["terms"], np.broadcast_to(exact[None, :], (N, tb.K)), f"{tag} terms")
-            truth = ref.truth(blk, tb, n, repr_, srcs, steps=steps, max_steps=7)
-            assert np.array_equal(np.isnan(got["terms"]), np.isnan(truth["terms"])), f"{tag}: NaN terms"
-            with np.errstate(invalid="ignore"):
-                err = np.abs(got["terms"].astype(np.float64) - want["terms"].astype(np.float64))
-                rel = err / (4 * eps * np.abs(want["terms"].astype(np.float64)))
-                terr = np.abs(got["terms"].astype(np.float64) - truth["terms"]) / ref.bounds(blk, tb, n, repr_, srcs)
-            if is_exp.any():
-                r = float(np.nanmax(np.where(err[:, is_exp] == 0, 0.0, rel[:, is_exp])))
-                worst["exp"] = max(worst["exp"], r)
-                assert r <= 1.0, f"{tag}: an EXP term misses 4 eps |want| by a factor of {r:.3g}"
-            if is_derived.any():
-                r = float(np.nanmax(terr[:, is_derived]))
-                worst["derived"] = max(worst["derived"], r)
-                assert r <= 1.0, f"{tag}: a term on a derived kind misses its bound by a factor of {r:.3g}"
-            # the reward of the whole table: within the terms' bounds and the K roundings of the sum
-            tp = np.abs(truth["terms"])
-            rb = ref.bounds(blk, tb, n, repr_, srcs).sum(axis=1) + 2 * (tb.K + 1) * eps * (tp.sum(axis=1) + abs(tb.termination_reward))
-            with np.errstate(invalid="ignore"):
-                r = float(np.nanmax(np.abs(got["reward"].astype(np.float64) - truth["reward"]) / rb))
-            assert np.array_equal(np.isnan(got["reward"]), np.isnan(truth["reward"])), f"{tag}: NaN rewards"
-            worst["reward"] = max(worst["reward"], r)
-            assert r <= 1.0, f"{tag}: the reward misses its bound by a factor of {r:.3g}"
-            # the bit-exact terms alone: reward, terms, done, fired and steps bit for bit; into a wider terms row too
-            xt = ref.make_table([t for t, e in zip(terms, exact) if e], conds, reward_clip=(-3.0, 2.5), termination_reward=-1.25)
-            want = ref.evaluate(blk, xt, n, repr_, srcs, steps=steps, max_steps=7)
-            got = evaluate(storage, xt, rows, n, N, T, repr_, tsrcs, steps=steps, max_steps=7, terms_ld=xt.K + 3, fill=np.nan)
-            all_ = np.ones((N, xt.K), bool)
-            same_or_both_nan(got["reward"], want["reward"], all_[:, 0], f"{tag} exact reward")
-            same_or_both_nan(np.ascontiguousarray(got["terms"][:, : xt.K]), want["terms"], all_, f"{tag} exact terms")
-            assert np.isnan(got["terms"][:, xt.K :]).all(), f"{tag}: the gap columns of a wider terms row were written"
-            for k in ("done", "fired", "steps"):
-                assert np.array_equal(got[k], want[k]), f"{tag}: exact {k}"
-    return worst
 
 
 @pytest.mark.parametrize("n,n_points,T,dtype", GRID)
@@ -156,7 +36,7 @@ def test_the_harness_equals_the_restatement(n, n_points, T, dtype):
     exponentials documented to 1 ulp each, and the two roundings of the weight); measured worst ratio over this grid 0.47 (the
     harness's exponential against NumPy's).  Terms on derived kinds against the float64 truth within
     ``env_evaluate_ref.bounds``: worst ratio 0.04; the reward of the whole table against the sum of its terms' bounds: 0.01."""
-    worst = check_against_the_restatement(emul_evaluate, n, n_points, T, dtype, "harness")
+    worst = check_evaluate_against_the_restatement(emul_evaluate, n, n_points, T, dtype, "harness")
     print("worst ratios:", {k: round(v, 4) for k, v in worst.items()})
 
 

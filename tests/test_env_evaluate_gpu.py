@@ -15,12 +15,11 @@ import env_observe_ref as oref
 import helpers
 import jaxsim_amd.api as js
 import step_bitwise_cases as sbc
+from env_cpu_support import check_evaluate_against_the_restatement, cond_list, make_block, make_sources, same_or_both_nan, SOURCE_ROWS, term_list, tiled_sources
 from env_gpu_support import CONTACT, DTYPES, MODELS, Guarded, InNaN, assert_same_bits, icub_data, same_words
 from jaxsim_amd import _lib, runtime
 from jaxsim_amd.runtime import DeviceArray, DeviceIndices, DeviceMask, DeviceMatrix, DeviceWords
 from jaxsim_amd.state import StateLayout
-from test_env_evaluate_cpu import SOURCE_ROWS, check_against_the_restatement, cond_list, make_sources, term_list
-from test_env_observe_cpu import make_block, same_or_both_nan, tiled_sources
 
 pytestmark = pytest.mark.gpu
 
@@ -63,7 +62,7 @@ def pattern_of(count, dtype):
 
 
 def device_evaluate(dm):
-    """The ``evaluate`` of tests/test_env_evaluate_cpu.py::check_against_the_restatement on the device.  Every output lies in a
+    """The ``evaluate`` of tests/test_env_evaluate_cpu.py::check_evaluate_against_the_restatement on the device.  Every output lies in a
     guarded buffer of a known bit pattern, two entries (rows) longer than N: every word outside reward[:N], done[:N], fired[:N],
     steps[:N] and columns < K of terms[:N] must keep its bits.  The gap columns of ``terms`` come back as ``fill``."""
 
@@ -116,7 +115,7 @@ def test_env_evaluate_keeps_the_contract_of_the_harness(models, key, dtype):
     dm = runtime.device_model(model, dtype)
     lay, T = StateLayout.of(model), dm.layout.tile
     assert oref.n_rows(lay.n_joints, lay.n_points) == lay.n_rows
-    worst = check_against_the_restatement(device_evaluate(dm), lay.n_joints, lay.n_points, T, dtype, key, sizes=sizes_of(T))
+    worst = check_evaluate_against_the_restatement(device_evaluate(dm), lay.n_joints, lay.n_points, T, dtype, key, sizes=sizes_of(T))
     print("worst ratios:", {k: round(v, 4) for k, v in worst.items()})
 
 
@@ -128,7 +127,7 @@ def test_a_wave_of_several_tiles_and_a_partial_last_wave(models, knobs, envs_per
     model, dtype = sbc.build_model("icub", models), np.float32
     dm = runtime.device_model(model, dtype)
     lay, T = StateLayout.of(model), dm.layout.tile
-    check_against_the_restatement(device_evaluate(dm), lay.n_joints, lay.n_points, T, dtype, f"E={envs_per_wave}", sizes=[2 * T + 1], seed=7)
+    check_evaluate_against_the_restatement(device_evaluate(dm), lay.n_joints, lay.n_points, T, dtype, f"E={envs_per_wave}", sizes=[2 * T + 1], seed=7)
 
 
 def test_the_widest_table_in_fp64_on_the_largest_tile(models):

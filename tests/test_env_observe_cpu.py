@@ -12,111 +12,16 @@ import pytest
 import env_observe_emul as emul
 import env_observe_ref as ref
 import jaxsim_amd.api as js
+from env_cpu_support import check_observe_against_the_restatement, Foreign, lib, make_block, refused, REPRS, special_envs, stub_data  # noqa: F401  (lib: a fixture)
 from jaxsim_amd import _lib, runtime
 from jaxsim_amd.data import JaxSimModelData
 from jaxsim_amd.model import VelRepr
 from jaxsim_amd.state import StateLayout
-from test_env_ops_cpu import Foreign, assert_same_bits, lib, refused, stub_data  # noqa: F401  (lib: a fixture)
 
 DTYPES = (np.float32, np.float64)
 SHAPES = ((23, 32), (12, 4), (2, 0), (0, 8))  # (n_joints, n_points)
 TILES = (1, 2, 4)
-REPRS = (ref.INERTIAL, ref.BODY, ref.MIXED)
-SOURCE_ROWS = (5, 0, 3)  # sources 0 and 2; source 1 does not exist
 GRID = [pytest.param(n, npt, T, dt, id=f"n{n}-p{npt}-T{T}-{np.dtype(dt).name}") for n, npt in SHAPES for T in TILES for dt in DTYPES]
-
-
-def batch_sizes(T):
-    return sorted({1, T, 2 * T + 1})
-
-
-def special_envs(n, N):
-    """(environment with a zero quaternion, environment with a NaN joint row) -- None where the batch is too small."""
-    return (N - 1 if N >= 2 else None), (N // 2 - 1 if N >= 3 and n > 0 else None)
-
-
-def make_block(n, n_points, N, dtype, seed):
-    """A state block ``[rows, N]``: |p| <= 2, velocities <= 5, quaternions 1e-3 off unit norm; one environment with a zero
-    quaternion and one with a NaN joint-position row where the batch has room for them."""
-    rng = np.random.default_rng(seed)
-    rows = ref.n_rows(n, n_points)
-    blk = rng.uniform(-1.0, 1.0, size=(rows, N))
-    p = rng.normal(size=(3, N))
-    blk[0:3] = p / np.linalg.norm(p, axis=0) * rng.uniform(0.0, 2.0, size=N)
-    q = rng.normal(size=(4, N))
-    blk[3:7] = q / np.linalg.norm(q, axis=0) * (1.0 + 1e-3 * rng.choice([-1.0, 1.0], size=N))
-    blk[7 + n : 13 + n] = rng.uniform(-5.0, 5.0, size=(6, N))
-    blk[13 + n : 13 + 2 * n] = rng.uniform(-5.0, 5.0, size=(n, N))
-    zero_q, nan_env = special_envs(n, N)
-    if zero_q is not None:
-        blk[3:7, zero_q] = 0.0
-    if nan_env is not None:
-        blk[7 + n // 2, nan_env] = np.nan
-    return blk.astype(dtype)
-
-
-def make_sources(N, dtype, seed):
-    rng = np.random.default_rng(seed + 1)
-    return [None if r == 0 else rng.uniform(-3.0, 3.0, size=(r, N)).astype(dtype) for r in SOURCE_ROWS]
-
-
-def tiled_sources(srcs, T):
-    """The sources as the harness and the kernel take them; the padding columns hold NaN."""
-    return [None if s is None else (ref.tile_block(s, T, pad=np.nan), s.shape[0]) for s in srcs]
-
-
-def same_or_both_nan(got, want, mask, what):
-    """Bit for bit where ``mask`` holds, a NaN comparing equal to any NaN."""
-    assert got.shape == want.shape and got.dtype == want.dtype, what
-    u = np.uint32 if got.dtype == np.float32 else np.uint64
-    same = (got.view(u) == want.view(u)) | (np.isnan(got) & np.isnan(want))
-    bad = ~same & mask
-    assert not bad.any(), f"{what}: {int(bad.sum())} words differ, first at {tuple(np.argwhere(bad)[0])}"
-
-
-def check_against_the_restatement(observe, n, n_points, T, dtype, what, seed=0):
-    """``observe(storage, slots, offset, scale, N, repr, sources, out_ld, out_dtype)`` -> ``[N, out_ld]`` (untouched words NaN)
-    against tests/env_observe_ref.py over the batch sizes and the three representations.  Returns the worst ratio of an
-    error to its bound per kind."""
-    rows = ref.n_rows(n, n_points)
-    slots = ref.full_table(rows, SOURCE_ROWS)
-    D = len(slots)
-    rng = np.random.default_rng(rows + T)
-    offsets, scales = rng.uniform(-2.0, 2.0, size=D).astype(dtype), rng.uniform(0.25, 4.0, size=D).astype(dtype)
-    worst = {}
-    for N in batch_sizes(T):
-        blk = make_block(n, n_points, N, dtype, seed=seed + 100 * N + rows)
-        srcs = make_sources(N, dtype, seed=N)
-        storage, tsrcs = ref.tile_block(blk, T, pad=np.nan), tiled_sources(srcs, T)
-        for repr_ in REPRS:
-            tag = f"{what} N={N} repr={repr_}"
-            exact = np.array([ref.bitwise(k, repr_) for k, _, _ in slots])
-            cols = np.broadcast_to(exact[None, :], (N, D))
-            # the + - x kinds, bit for bit: as they are, and with an offset and a scale; into a wider row too
-            for off, sc in ((0.0, 1.0), (offsets, scales)):
-                want = ref.observe(blk, slots, off, sc, n, repr_, srcs)
-                got = observe(storage, slots, off, sc, N, repr_, tsrcs, D, dtype)
-                same_or_both_nan(got, want, cols, tag)
-            wide = observe(storage, slots, offsets, scales, N, repr_, tsrcs, D + 3, dtype)
-            assert np.isnan(wide[:, D:]).all(), f"{tag}: the gap columns of a wider row were written"
-            same_or_both_nan(np.ascontiguousarray(wide[:, :D]), want, cols, f"{tag} out_ld=D+3")
-            if dtype == np.float64:  # rounded once, at the store
-                got32 = observe(storage, slots, offsets, scales, N, repr_, tsrcs, D, np.float32)
-                same_or_both_nan(got32, want.astype(np.float32), cols, f"{tag} out_dtype=float32")
-            # the other kinds against the float64 truth on the stored inputs (offset 0, scale 1: the slot adds no rounding)
-            got = observe(storage, slots, 0.0, 1.0, N, repr_, tsrcs, D, dtype)
-            truth = ref.observe(blk, slots, 0.0, 1.0, n, repr_, srcs, dtype=np.float64)
-            bound = ref.bounds(slots, blk, n, dtype)
-            err = np.abs(got.astype(np.float64) - truth)
-            for kind in ref.COMPONENTS:
-                sel = (slots[:, 0] == kind) & ~exact
-                if not sel.any():
-                    continue
-                assert np.isfinite(got[:, sel]).all(), f"{tag}: a derived value of kind {kind} is not finite"
-                ratio = float((err[:, sel] / bound[:, sel]).max())
-                worst[kind] = max(worst.get(kind, 0.0), ratio)
-                assert ratio <= 1.0, f"{tag}: kind {kind} misses its bound by a factor of {ratio:.3g}"
-    return worst
 
 
 def emul_observe(n, n_points, T):
@@ -136,7 +41,7 @@ def test_the_harness_equals_the_restatement(n, n_points, T, dtype):
     (64 eps (1 + |l| + |p||w|)).  Measured worst ratios of an error to its bound over this grid in float32: unit quaternion
     0.16, rotation 0.18, projected gravity 0.18, Body velocity 0.04; in float64 the harness and the truth are the same
     arithmetic and the ratios are 0."""
-    worst = check_against_the_restatement(emul_observe(n, n_points, T), n, n_points, T, dtype, "harness")
+    worst = check_observe_against_the_restatement(emul_observe(n, n_points, T), n, n_points, T, dtype, "harness")
     print("worst error / bound per kind:", {k: round(v, 4) for k, v in worst.items()})
 
 

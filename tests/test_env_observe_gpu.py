@@ -15,11 +15,11 @@ import helpers
 import jaxsim_amd as ja
 import jaxsim_amd.api as js
 import step_bitwise_cases as sbc
+from env_cpu_support import check_observe_against_the_restatement, make_block, make_sources, same_or_both_nan, SOURCE_ROWS, tiled_sources
 from env_gpu_support import DTYPES, MODELS, Guarded, InNaN, assert_same_bits, icub_data, upload_flat
 from jaxsim_amd import _lib, runtime
 from jaxsim_amd.runtime import DeviceArray, DeviceMatrix
 from jaxsim_amd.state import StateLayout
-from test_env_observe_cpu import SOURCE_ROWS, check_against_the_restatement, make_block, make_sources, same_or_both_nan, tiled_sources
 
 pytestmark = pytest.mark.gpu
 
@@ -48,7 +48,7 @@ def env_observe(dm, table, state_ptr, source_ptrs, N, repr_, out_ptr, out_dtype,
 
 
 def device_observe(dm):
-    """The ``observe`` of tests/test_env_observe_cpu.py::check_against_the_restatement on the device.  The tensor lies in a
+    """The ``observe`` of tests/test_env_observe_cpu.py::check_observe_against_the_restatement on the device.  The tensor lies in a
     guarded buffer of a known bit pattern, two rows longer than N: every word outside columns < D of rows < N must keep
     its bits -- the gap columns, the rows behind N - 1, the guards.  The gap columns come back as NaN."""
 
@@ -86,7 +86,7 @@ def test_env_observe_keeps_the_contract_of_the_harness(models, key, dtype):
     dm = runtime.device_model(model, dtype)
     lay, T = StateLayout.of(model), dm.layout.tile
     assert (dm.layout.n_rows, dm.layout.n_joints) == (lay.n_rows, lay.n_joints) and ref.n_rows(lay.n_joints, lay.n_points) == lay.n_rows
-    worst = check_against_the_restatement(device_observe(dm), lay.n_joints, lay.n_points, T, dtype, key)
+    worst = check_observe_against_the_restatement(device_observe(dm), lay.n_joints, lay.n_points, T, dtype, key)
     print("worst error / bound per kind:", {k: round(v, 4) for k, v in worst.items()})
 
 
@@ -98,7 +98,7 @@ def test_a_wave_of_several_tiles_and_a_partial_last_wave(models, knobs, envs_per
     model, dtype = sbc.build_model("icub", models), np.float32
     dm = runtime.device_model(model, dtype)
     lay = StateLayout.of(model)
-    check_against_the_restatement(device_observe(dm), lay.n_joints, lay.n_points, dm.layout.tile, dtype, f"E={envs_per_wave}", seed=7)
+    check_observe_against_the_restatement(device_observe(dm), lay.n_joints, lay.n_points, dm.layout.tile, dtype, f"E={envs_per_wave}", seed=7)
 
 
 @pytest.mark.parametrize("key", ["icub", "quadruped_rigid"])

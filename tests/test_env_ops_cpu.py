@@ -4,16 +4,14 @@ index functions of csrc/jxs_env_ops.h (driven over every word by the host harnes
 the refusals of the C ABI, and the host logic of the Python layer."""
 
 import ctypes as C
-import types
 
 import numpy as np
 import pytest
 
 import env_ops_emul as emul
 import env_ops_ref as ref
+from env_cpu_support import Foreign, assert_same_bits, bits, lib, refused, stub_data  # noqa: F401  (lib: a fixture)
 from jaxsim_amd import _lib, runtime
-from jaxsim_amd.data import JaxSimModelData
-from jaxsim_amd.model import VelRepr
 from jaxsim_amd.state import tile_block, untile_block
 
 DTYPES = (np.float32, np.float64)
@@ -21,16 +19,6 @@ GRID = [pytest.param(rows, T, N, dt, id=f"r{rows}-T{T}-N{N}-{np.dtype(dt).name}"
 
 
 FLAG_GRID = [p for p in GRID if p.values[0] >= 5]  # (a block of one row holds no quaternion)
-
-
-def bits(a):
-    return a.view(ref.bits_dtype(a.dtype))
-
-
-def assert_same_bits(got, want, what=""):
-    assert got.dtype == want.dtype and got.shape == want.shape, what
-    differ = bits(got) != bits(want)
-    assert not differ.any(), f"{what}: {int(differ.sum())} of {differ.size} words differ, first at {int(np.argmax(differ))}"
 
 
 def masks_of(N, rng):
@@ -223,21 +211,6 @@ def test_environments_per_wave_stay_between_a_tile_and_the_larger_of_a_tile_and_
 
 
 # ---- the C ABI refuses bad arguments without a device ---------------------------------------------------------------
-@pytest.fixture(scope="module")
-def lib():
-    if not _lib.LIB_PATH.exists():
-        import __graft_entry__
-
-        __graft_entry__.build()
-    return _lib.load()
-
-
-def refused(lib, rc, *words):
-    assert rc == -1
-    msg = lib.jxs_last_error().decode()
-    assert msg and any(w in msg for w in words), msg
-
-
 def test_cabi_exports_and_refusals(lib):
     for name in ("jxs_env_select", "jxs_env_copy", "jxs_env_flags"):
         assert name in _lib.EXPORTED_SYMBOLS and hasattr(lib, name)
@@ -269,13 +242,6 @@ def test_cabi_exports_and_refusals(lib):
 
 
 # ---- host logic of the Python layer ---------------------------------------------------------------------------------
-class Foreign:
-    """What another framework hands over: a ``__cuda_array_interface__`` over memory this library does not own."""
-
-    def __init__(self, shape, typestr, ptr=0x1000, strides=None):
-        self.__cuda_array_interface__ = {"shape": shape, "typestr": typestr, "data": (ptr, False), "strides": strides, "version": 3}
-
-
 def test_host_masks_are_normalised_or_refused():
     assert np.array_equal(runtime.host_mask([True, False, True], 3), np.array([1, 0, 1], np.uint8))
     assert np.array_equal(runtime.host_mask(np.array([0, 2, 255], np.uint8), 3), np.array([0, 1, 1], np.uint8))
@@ -311,14 +277,6 @@ def test_foreign_device_arrays_are_used_as_they_are_or_refused():
                 Foreign((0,), "<i4")):  # fmt: skip
         with pytest.raises(ValueError):
             runtime.as_device_indices(bad, 9, unique=True)
-
-
-def stub_data(model, N, dtype, tile=2):
-    """A data object around a state that is no device buffer: every refusal below must come before the first device call."""
-    from jaxsim_amd.state import StateLayout
-
-    state = types.SimpleNamespace(rows=StateLayout.of(model).n_rows, cols=N, tile=tile, dtype=np.dtype(dtype), ptr=None)
-    return JaxSimModelData(model, state, VelRepr.Mixed, True)
 
 
 def test_mismatched_arguments_are_refused_on_the_host(models):

@@ -12,6 +12,7 @@ import env_random_emul as emul
 import env_random_ref as ref
 import jaxsim_amd as ja
 import jaxsim_amd.api as js
+from env_cpu_support import check_contract
 from jaxsim_amd import _lib, robots
 from jaxsim_amd.state import StateLayout
 
@@ -27,46 +28,6 @@ def masks_of(N):
     last = np.zeros(N, np.uint8)
     last[N - 1] = 1
     return {"null": None, "none": np.zeros(N, np.uint8), "all": np.full(N, 3, np.uint8), "alternating": (np.arange(N) % 2 == 0).astype(np.uint8), "last": last}
-
-
-def named_words(rows, N, T, take):
-    """For every flat word of the storage: does it belong to an environment the mask names?"""
-    env = eref.word_env(rows, N, T)
-    out = np.zeros(env.shape, dtype=bool)
-    real = env < N
-    out[real] = take[env[real]]
-    return out
-
-
-def check_contract(got, before, mask, n, n_points, N, T, bounds, seed, draw, first_env, floating, repr_, what=""):
-    """The contract of jxs_env_randomize on a tiled storage ``got`` that held ``before``."""
-    dt = before.dtype
-    u, eps = eref.bits_dtype(dt), float(np.finfo(dt).eps)
-    L = ref.Rows(n, n_points)
-    with np.errstate(all="ignore"):  # (the environments that keep their random bits hold NaNs and infinities)
-        want, exact, take = ref.randomize(before, mask, n, n_points, N, T, bounds, seed, draw, first_env, floating, repr_)
-    named = named_words(L.rows, N, T, take)
-    assert (got.view(u)[~named] == before.view(u)[~named]).all(), f"{what}: words of unnamed environments or of padding columns changed"
-    tk = np.nonzero(take)[0]
-    if tk.size == 0:
-        return
-    g = ref.untile(got, L.rows, N, T)[:, tk]
-    w = ref.untile(want, L.rows, N, T)[:, tk]
-    bw = L.bitwise(floating, repr_)
-    differ = g.view(u)[bw] != w.view(u)[bw]
-    assert not differ.any(), f"{what}: {int(differ.sum())} words of the uniform / zero rows differ"
-    assert np.isfinite(g).all(), what
-    dq = np.abs(g[L.quat : L.quat + 4].astype(np.float64) - exact[L.quat : L.quat + 4, tk]).max()
-    assert dq <= 16 * eps, f"{what}: quaternion off by {dq / eps:.1f} eps"
-    if floating and repr_ != ref.INERTIAL:
-        x = ref.variables(bounds, first_env + tk, seed, draw)
-        lin, ang = x[6 + n : 9 + n], x[9 + n : 12 + n]
-        v = ref.velocity_of_block(L, g, lin, ang, repr_)
-        scale = np.maximum(1.0, np.linalg.norm(lin, axis=0) + np.linalg.norm(g[0:3].astype(np.float64), axis=0) * np.linalg.norm(ang, axis=0))
-        dv = (np.abs(g[L.vlin : L.vlin + 6].astype(np.float64) - v) / scale).max()
-        assert dv <= 32 * eps, f"{what}: base velocity off by {dv / eps:.1f} eps (scaled)"
-    if not floating:
-        assert (g.view(u)[L.vlin : L.vlin + 6] == 0).all(), f"{what}: a fixed base must get six exact zeros"
 
 
 def test_philox_known_answers():

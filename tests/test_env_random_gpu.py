@@ -14,11 +14,11 @@ import helpers
 import jaxsim_amd as ja
 import jaxsim_amd.api as js
 import step_bitwise_cases as sbc
+from env_cpu_support import check_contract
 from env_gpu_support import CONTACT, DTYPES, MODELS, Guarded, assert_same_bits, upload_flat
 from jaxsim_amd import _lib, runtime
 from jaxsim_amd.runtime import DeviceMask
 from jaxsim_amd.state import StateLayout
-from test_env_random_cpu import check_contract
 
 pytestmark = pytest.mark.gpu
 

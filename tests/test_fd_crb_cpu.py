@@ -23,11 +23,11 @@ import helpers
 import jaxsim_amd as ja
 import jaxsim_amd.api as js
 import oracle
-import test_maxcoord_independent as tmi
+import parity_cases as pc
+from coriolis_ref import TEXTS, model_of
 from jaxsim_amd import _lib
 from oracle import VelRepr
 from oracle import refstep as rs
-from test_coriolis_cpu import TEXTS, model_of
 
 REPS = (VelRepr.Inertial, VelRepr.Body, VelRepr.Mixed)  # index = the force representation code of the kernel
 # fp32: the gates are the worst relative error of the emulation against the fp64 restatement (seed 3, N = 4, the six input
@@ -87,10 +87,10 @@ def test_restatement_differs_from_aba_for_body_wrenches_on_a_base_offset_model()
         assert (rel(crb, aba) < 1e-10) == same
 
 
-@pytest.mark.parametrize("name", list(tmi.TEXTS))
+@pytest.mark.parametrize("name", list(pc.MAXCOORD_TEXTS))
 def test_restatement_equals_maximal_coordinates(name):
-    text, model, d, tau, f = tmi.case(name, 4, seed=3)  # (Mixed; no wrenches on the offset-base models)
-    vd, sdd = tmi.truth(text, model, d, tau, f)
+    text, model, d, tau, f = pc.maxcoord_case(name, 4, seed=3)  # (Mixed; no wrenches on the offset-base models)
+    vd, sdd = pc.maxcoord_truth(text, model, d, tau, f)
     d._model = model
     cvd, csdd = fref.forward_dynamics_crb(model, d, joint_forces=tau, link_forces=f)
     assert rel(csdd, sdd) < 1e-10

@@ -20,7 +20,6 @@ import helpers
 import jaxsim_amd as ja
 import jaxsim_amd.api as js
 from jaxsim_amd import robots
-from oracle import refmath as rm
 
 TEXTS = {
     "icub": lambda: robots.icub23_urdf(),
@@ -127,56 +126,6 @@ def test_fixed_base_bias_includes_the_stored_base_velocity():
 
 
 # ---- the restatement against a finite difference in time -------------------------------------------------------------
-def _advance(model, d, I, h):
-    """The state after time h at constant I_nu (s'' = 0; the base moves with constant velocity in representation I)."""
-    W_H_B = d.base_transform.astype(np.float64)
-    nu = d.generalized_velocity(fr.REPS[I]).astype(np.float64)
-    vB, w = nu[:, :3], nu[:, 3:6]
-    R, p = W_H_B[:, :3, :3], W_H_B[:, :3, 3]
-    if I == 0:  # constant W_v_WB: a screw motion, H(t) = expm(t [w]^ ; t v) H(0)
-        X = np.zeros((d.batch_size, 4, 4))
-        X[:, :3, :3] = rm.wedge(w) * h
-        X[:, :3, 3] = vB * h
-        H = np.stack([_expm(x) for x in X]) @ W_H_B
-    elif I == 1:  # constant B_v_WB: H(t) = H(0) expm(t [w]^ ; t v)
-        X = np.zeros((d.batch_size, 4, 4))
-        X[:, :3, :3] = rm.wedge(w) * h
-        X[:, :3, 3] = vB * h
-        H = W_H_B @ np.stack([_expm(x) for x in X])
-    else:  # constant mixed velocity: p(t) = p + t pdot, R(t) = expm(t [w]^) R
-        H = W_H_B.copy()
-        H[:, :3, 3] = p + h * vB
-        H[:, :3, :3] = np.stack([_expm3(x) for x in rm.wedge(w) * h]) @ R
-    q = np.stack([_quat(Rk) for Rk in H[:, :3, :3]])
-    s = d.joint_positions.astype(np.float64) + h * d.joint_velocities.astype(np.float64)
-    from oracle import refstep as rs
-
-    W_v = rs.other_representation_to_inertial(nu[:, :6], fr.REPS[I], H, is_force=False)
-    out = dataclasses.replace(d, base_position=H[:, :3, 3].copy(), base_quaternion=q, joint_positions=s,
-                              base_linear_velocity=W_v[:, :3].copy(), base_angular_velocity=W_v[:, 3:].copy())  # fmt: skip
-    return out.update_caches(model)
-
-
-def _expm(X):
-    out, term = np.eye(4), np.eye(4)
-    for k in range(1, 30):
-        term = term @ X / k
-        out = out + term
-    return out
-
-
-def _expm3(X):
-    return _expm(np.pad(X, ((0, 1), (0, 1))))[:3, :3]
-
-
-def _quat(R):
-    w = np.sqrt(max(0.0, 1.0 + R[0, 0] + R[1, 1] + R[2, 2])) / 2.0
-    x = np.copysign(np.sqrt(max(0.0, 1.0 + R[0, 0] - R[1, 1] - R[2, 2])) / 2.0, R[2, 1] - R[1, 2])
-    y = np.copysign(np.sqrt(max(0.0, 1.0 - R[0, 0] + R[1, 1] - R[2, 2])) / 2.0, R[0, 2] - R[2, 0])
-    z = np.copysign(np.sqrt(max(0.0, 1.0 - R[0, 0] - R[1, 1] + R[2, 2])) / 2.0, R[1, 0] - R[0, 1])
-    return np.array([w, x, y, z])
-
-
 @pytest.mark.parametrize("name,which", [("anymal", "links"), ("lumped", "frames"), ("cartpole", "frames"), ("chain9f", "links")])
 @pytest.mark.parametrize("I", [0, 1, 2])
 @pytest.mark.parametrize("O", [0, 1, 2])
@@ -185,8 +134,8 @@ def test_restatement_bias_is_the_time_derivative_of_the_velocity(name, which, I,
     d = with_rep(model, cr.random_data(model, 3, seed=12), I)
     P, H = targets(model, which)
     h = 1e-5
-    vp = fr.restate(model, with_rep(model, _advance(model, d, I, h), I), P, H, I, O)["v"]
-    vm = fr.restate(model, with_rep(model, _advance(model, d, I, -h), I), P, H, I, O)["v"]
+    vp = fr.restate(model, with_rep(model, fr.advance(model, d, I, h), I), P, H, I, O)["v"]
+    vm = fr.restate(model, with_rep(model, fr.advance(model, d, I, -h), I), P, H, I, O)["v"]
     a = fr.restate(model, d, P, H, I, O)["a"]
     assert rel((vp - vm) / (2 * h), a) < 1e-6
 

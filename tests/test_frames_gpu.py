@@ -177,9 +177,7 @@ def test_inertial_body_identity_of_the_bias_gpu(models):
 
 def _advance_mixed(model, d, h):
     """The state after time h at constant mixed generalized velocity."""
-    from test_frames_cpu import _advance
-
-    return _advance(model, with_rep(model, d, 2), 2, h)
+    return fr.advance(model, with_rep(model, d, 2), 2, h)
 
 
 @pytest.mark.gpu

@@ -11,17 +11,13 @@ import helpers
 import jaxsim_amd as ja
 import jaxsim_amd.api as js
 import oracle
+import parity_cases as pc
+from helpers import REP, to_gpu
 from jaxsim_amd import runtime
 from oracle import VelRepr
+from parity_cases import ALL, OCTOPOD_FEET_4, OCTOPOD_FEET_16, RELAXED_CASES, REPS, RIGID_CASES, reduced_qp  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-REP = {VelRepr.Inertial: ja.VelRepr.Inertial, VelRepr.Body: ja.VelRepr.Body, VelRepr.Mixed: ja.VelRepr.Mixed}
-ALL = ["box", "sphere", "pendulum", "double_pendulum", "cartpole", "chain5", "chain9f", "anymal", "icub", "icub16"]
-
-
-def to_gpu(model, d: oracle.OracleData) -> js.data.JaxSimModelData:
-    return js.data.JaxSimModelData.from_state_block(model, helpers.odata_to_block(model, d), REP[d.velocity_representation])
 
 
 def test_native_library_is_the_one_in_tree():
@@ -382,17 +378,11 @@ def test_two_wave_step_matches_oracle_and_single_wave_gpu(models, name, dtype, k
         assert not np.array_equal(duo, solo), "the two-wave variant did not run"
 
 
-# ---- Runge-Kutta 4 (api/integrators.py:91-167) --------------------------------------------------
-def _rk4(model):
-    # softer ground than the zoo default: explicit RK4 is outside its stability region at K = 1e6
-    soft = ja.SoftContactsParams.build(K=2e4, D=60.0, mu=0.6)
-    return helpers.with_params(model, integrator=ja.IntegratorType.RungeKutta4, contact_params=soft)
-
-
+# ---- Runge-Kutta 4 (api/integrators.py:91-167; the softer ground: pc.rk4) --------------------------------------------------
 @pytest.mark.parametrize("name", ["box", "sphere", "cartpole", "chain9f", "anymal", "icub16", "icub"])
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])
 def test_rk4_step_matches_oracle_gpu(models, name, dtype):
-    model = _rk4(models(name))
+    model = pc.rk4(models(name))
     N = 70
     d = models.random_data(name, N, seed=31, dtype=dtype)
     tau, f = helpers.random_inputs(model, N, 32, dtype)
@@ -408,19 +398,8 @@ def test_controlled_rollout_equals_the_step_loop_gpu(models, name, kind):
     steps fuse, one launch per step with the step's rows gathered by a strided device copy otherwise (RungeKutta4,
     RigidContacts, several point chunks).  Against the oracle stepping with tau[k]; equal to K single steps on the
     device; not the rollout that holds tau[0]."""
-    from jaxsim_amd import robots
-
     K, N = 6, 37
-    if name == "icub80":
-        model = ja.JaxSimModel.build_from_model_description(robots.icub23_urdf(sole_boxes_per_foot=5))
-        d = oracle.random_model_data(model, batch_size=N, seed=3, base_pos_bounds=((-1, -1, 0.56), (1, 1, 0.66)), base_rpy_bounds=((-0.3, -0.3, -3), (0.3, 0.3, 3)))
-    else:
-        model = models(name)
-        d = models.random_data(name, N, seed=21)
-    if kind == "rk4":
-        model = _rk4(model)
-    if kind == "rigid":
-        model = helpers.rigid_model(model, helpers.ANYMAL_FEET_4, K=1e4, D=2e2)
+    model, d = pc.rollout_case(models, name, kind, N, seed=21)
     n = model.dofs()
     tau = np.random.default_rng(11).uniform(-3, 3, size=(K, N, n))
     ref = d
@@ -450,21 +429,8 @@ def test_recorded_rollout_returns_every_step_gpu(models, name, kind, seq):
     stacked outputs of the reference's jax.lax.scan over step), stored from registers inside the fused launch or copied
     per step where the steps do not fuse.  Every recorded state against the oracle; the last one is the final state;
     recording does not change the rollout (bitwise)."""
-    from jaxsim_amd import robots
-
     K, N = 5, 37
-    if name == "icub80":
-        model = ja.JaxSimModel.build_from_model_description(robots.icub23_urdf(sole_boxes_per_foot=5))
-        d = oracle.random_model_data(model, batch_size=N, seed=3, base_pos_bounds=((-1, -1, 0.56), (1, 1, 0.66)), base_rpy_bounds=((-0.3, -0.3, -3), (0.3, 0.3, 3)))
-    else:
-        model = models(name)
-        d = models.random_data(name, N, seed=23)
-    if kind == "rk4":
-        model = _rk4(model)
-    if kind == "rigid":
-        model = helpers.rigid_model(model, helpers.ANYMAL_FEET_4, K=1e4, D=2e2)
-    if kind == "disabled":
-        model = helpers.enable_points(model, [0, 1, 2, 3, 8, 9, 10, 11])
+    model, d = pc.rollout_case(models, name, kind, N, seed=23)
     n = model.dofs()
     tau = np.random.default_rng(13).uniform(-3, 3, size=(K, N, n))
     if not seq:
@@ -486,12 +452,9 @@ def test_rk4_with_more_points_than_lanes_gpu(models, dtype, tol):
     """[round 4] RungeKutta4 + SoftContacts with 80 collidable points on 32 lanes: three chunks, the stage data of the
     chunks behind the first in the LDS (jxs_core.h contact_chunk); one step against the oracle, then ten in place
     (the deformation rows are read at every stage and written at the last) -- was refused up to round 3."""
-    from jaxsim_amd import robots
-
-    model = _rk4(ja.JaxSimModel.build_from_model_description(robots.icub23_urdf(sole_boxes_per_foot=5)))
+    model = pc.rk4(pc.icub80())
     N = 37
-    d = oracle.random_model_data(model, batch_size=N, seed=3, dtype=dtype, base_pos_bounds=((-1, -1, 0.56), (1, 1, 0.66)),
-                                 base_rpy_bounds=((-0.3, -0.3, -3), (0.3, 0.3, 3)))  # fmt: skip
+    d = pc.icub80_data(model, N, dtype)
     rng = np.random.default_rng(5)
     d.tangential_deformation[:] = (1e-3 * rng.normal(size=d.tangential_deformation.shape)).astype(dtype)
     tau, f = helpers.random_inputs(model, N, 7, dtype)
@@ -509,7 +472,7 @@ def test_rk4_with_more_points_than_lanes_gpu(models, dtype, tol):
 
 @pytest.mark.parametrize("rep", [VelRepr.Inertial, VelRepr.Body, VelRepr.Mixed])
 def test_rk4_link_force_representations_gpu(models, rep):
-    model = _rk4(models("icub"))
+    model = pc.rk4(models("icub"))
     d = models.random_data("icub", 33, seed=33, rep=rep)
     tau, f = helpers.random_inputs(model, 33, 34, np.float64)
     ref = oracle.step(model, d, link_forces=f, joint_force_references=tau)
@@ -518,14 +481,14 @@ def test_rk4_link_force_representations_gpu(models, rep):
 
 
 def test_rk4_rollout_and_free_fall_gpu(models):
-    model = _rk4(models("icub"))
+    model = pc.rk4(models("icub"))
     d = models.random_data("icub", 20, seed=35)
     out = js.model.rollout(model, to_gpu(model, d), 10).state_block()
     for _ in range(10):
         d = oracle.step(model, d)
     assert helpers.rel_err(out, helpers.odata_to_block(model, d)) < 1e-8
     # constant acceleration is integrated exactly by RK4
-    box = _rk4(models("box"))
+    box = pc.rk4(models("box"))
     v0 = np.array([0.3, -0.2, 1.0])
     d0 = oracle.OracleData.build(box, base_position=[0.0, 0.0, 5.0], base_linear_velocity=v0)
     blk = js.model.rollout(box, to_gpu(box, d0), 50).state_block()
@@ -534,39 +497,11 @@ def test_rk4_rollout_and_free_fall_gpu(models):
     np.testing.assert_allclose(blk[0:3, 0], expect, rtol=0, atol=1e-12)
 
 
-# ---- RigidContacts (rbda/contacts/rigid.py:176-539; BASELINE.json config 5) ----------------------
-RIGID_CASES = {
-    "box4": ("box", [0, 1, 2, 3], dict(K=1e5)),
-    "anymal16": ("anymal", helpers.ANYMAL_FEET_16, dict(K=1e4, D=1e2)),
-    "anymal4": ("anymal", helpers.ANYMAL_FEET_4, dict()),
-    "chain9f6": ("chain9f", [0, 1, 2, 3, 8, 9], dict(K=1e3, mu=0.8)),
-    "serial12f": ("serial12f", list(range(16)), dict(K=1e3, mu=0.8)),  # two contact links eleven joints apart
-    "icub8": ("icub16", [0, 1, 2, 3, 8, 9, 10, 11], dict(K=1e4)),
-    "planar_biped": ("planar_biped", list(range(16)), dict(K=1e4)),  # [round 5] six parallel joint axes between the two feet
-    "planar10f": ("planar10f", list(range(16)), dict(K=1e3, mu=0.8)),
-    # <= 4 points in a 32-lane group: the row-distributed register solver with the general Delassus sweeps
-    # (two points per foot: no merged sweep)
-    "icub4": ("icub16", [2, 9, 10, 11], dict(K=1e4)),
-    "anymal2": ("anymal", [0, 16], dict()),  # merged sweeps and the 12-row solver with identity padding
-}
-
-
-@pytest.fixture()
-def reduced_qp():
-    """The kernel solves the reduced statement of the reference's QP (oracle/refrigid.py)."""
-    from oracle import refrigid
-
-    refrigid.REDUCED_QP = True
-    yield refrigid
-    refrigid.REDUCED_QP = False
-
-
+# ---- RigidContacts (the cases: parity_cases.RIGID_CASES) ----------------------
 @pytest.mark.parametrize("key", list(RIGID_CASES))
 def test_rigid_step_matches_oracle_gpu(models, reduced_qp, key):
-    name, idx, params = RIGID_CASES[key]
-    model = helpers.rigid_model(models(name), idx, **params)
     N = 21  # not a multiple of the environments per wave
-    d = models.random_data(name, N, seed=5)
+    model, d = pc.rigid_case(models, key, N, seed=5)
     tau, f = helpers.random_inputs(model, N, 7, np.float64)
     ref = oracle.step(model, d, link_forces=f, joint_force_references=tau)
     out = js.model.step(model, to_gpu(model, d), link_forces=f, joint_force_references=tau)
@@ -595,9 +530,7 @@ def test_rigid_step_fp32_gpu(models, reduced_qp, key, tol):
     3e-6 .. 6e-5 on the articulated models, 1e-3 on the box: 1 kg, K = 1e5 with centimetres of
     penetration, i.e. contact forces of 1e3 N on four coplanar points whose 12x12 Delassus matrix has
     rank 6 plus the 1e-6 shift)."""
-    name, idx, params = RIGID_CASES[key]
-    model = helpers.rigid_model(models(name), idx, **params)
-    d = models.random_data(name, 40, seed=5, dtype=np.float32)
+    model, d = pc.rigid_case(models, key, 40, seed=5, dtype=np.float32)
     ref = oracle.step(model, helpers.upcast(d))
     out = js.model.step(model, to_gpu(model, d))
     blk = out.state_block()
@@ -610,7 +543,7 @@ def test_rigid_step_fp32_gpu(models, reduced_qp, key, tol):
 @pytest.mark.parametrize("dtype,atol", [(np.float64, 1e-4), (np.float32, 2e-4)])
 def test_rigid_box_settles_known_answer_gpu(models, dtype, atol):
     """reference tests/test_simulations.py:245-292."""
-    model = helpers.rigid_model(models("box"), [0, 1, 2, 3], build=dict(solver_options={"solver_tol": 1e-3}), K=1e5)
+    model = pc.settling_box(models, "rigid")
     d = oracle.OracleData.build(model, base_position=[0.0, 0.0, 0.2], velocity_representation=VelRepr.Inertial, dtype=dtype)
     out = js.model.rollout(model, to_gpu(model, d), 1000).state_block()
     assert abs(out[0, 0]) < 1e-6 and abs(out[1, 0]) < 1e-6
@@ -634,15 +567,14 @@ def test_rigid_models_carry_the_tangential_rows_through(models, kind):
 def test_rigid_rk4_step_matches_oracle_gpu(models, reduced_qp, key):
     """RungeKutta4 with RigidContacts: QP forces at each stage, impact on the integrated state; the
     reference runs its rigid-contact test for every integrator (tests/test_simulations.py:245)."""
-    name, idx, params = RIGID_CASES[key]
-    model = helpers.with_params(helpers.rigid_model(models(name), idx, **params), integrator=ja.IntegratorType.RungeKutta4)
     N = 21
-    d = models.random_data(name, N, seed=5)
+    model, d = pc.rigid_case(models, key, N, seed=5)
+    model = helpers.with_params(model, integrator=ja.IntegratorType.RungeKutta4)
     tau, f = helpers.random_inputs(model, N, 7, np.float64)
     ref = oracle.step(model, d, link_forces=f, joint_force_references=tau)
     out = js.model.step(model, to_gpu(model, d), link_forces=f, joint_force_references=tau)
     assert helpers.rel_err(out.state_block(), helpers.odata_to_block(model, ref)) < 1e-7
-    d32 = models.random_data(name, N, seed=5, dtype=np.float32)
+    _, d32 = pc.rigid_case(models, key, N, seed=5, dtype=np.float32)
     out32 = js.model.step(model, to_gpu(model, d32)).state_block()
     ref32 = oracle.step(model, helpers.upcast(d32))
     err32 = helpers.rel_err(out32, helpers.odata_to_block(model, ref32))
@@ -653,8 +585,7 @@ def test_rigid_rk4_step_matches_oracle_gpu(models, reduced_qp, key):
 @pytest.mark.parametrize("dtype,atol", [(np.float64, 1e-4), (np.float32, 2e-4)])
 def test_rigid_rk4_box_settles_known_answer_gpu(models, dtype, atol):
     """reference tests/test_simulations.py:245-292 with integrator = RungeKutta4."""
-    model = helpers.rigid_model(models("box"), [0, 1, 2, 3], build=dict(solver_options={"solver_tol": 1e-3}), K=1e5)
-    model = helpers.with_params(model, integrator=ja.IntegratorType.RungeKutta4)
+    model = pc.settling_box(models, "rigid", ja.IntegratorType.RungeKutta4)
     d = oracle.OracleData.build(model, base_position=[0.0, 0.0, 0.2], velocity_representation=VelRepr.Inertial, dtype=dtype)
     out = js.model.rollout(model, to_gpu(model, d), 1000).state_block()
     assert abs(out[0, 0]) < 1e-6 and abs(out[1, 0]) < 1e-6
@@ -665,16 +596,14 @@ def test_rigid_rk4_box_settles_known_answer_gpu(models, dtype, atol):
 def test_rk4fast_step_matches_oracle_gpu(models, reduced_qp, kind, key):
     """RungeKutta4Fast (api/integrators.py:170-276) with the contact models without contact state,
     against oracle/refstep.py::rk4fast_integration (the reference's function as written)."""
-    name, idx, params = (RELAXED_CASES if kind == "relaxed" else RIGID_CASES)[key]
-    make = helpers.relaxed_model if kind == "relaxed" else helpers.rigid_model
-    model = helpers.with_params(make(models(name), idx, **params), integrator=ja.IntegratorType.RungeKutta4Fast)
     N = 21
-    d = models.random_data(name, N, seed=5)
+    model, d = pc.contact_case(models, kind, key, N, seed=5)
+    model = helpers.with_params(model, integrator=ja.IntegratorType.RungeKutta4Fast)
     tau, f = helpers.random_inputs(model, N, 7, np.float64)
     ref = oracle.step(model, d, link_forces=f, joint_force_references=tau)
     out = js.model.step(model, to_gpu(model, d), link_forces=f, joint_force_references=tau)
     assert helpers.rel_err(out.state_block(), helpers.odata_to_block(model, ref)) < (1e-10 if kind == "relaxed" else 1e-7)
-    d32 = models.random_data(name, N, seed=5, dtype=np.float32)
+    _, d32 = pc.contact_case(models, kind, key, N, seed=5, dtype=np.float32)
     out32 = js.model.step(model, to_gpu(model, d32)).state_block()
     ref32 = oracle.step(model, helpers.upcast(d32))
     err32 = helpers.rel_err(out32, helpers.odata_to_block(model, ref32))
@@ -693,9 +622,7 @@ def test_mfma_cholesky_equals_the_vector_path_bitwise_gpu(models, kind, key, mon
     random states and of standing ones (every sole point active)."""
     from jaxsim_amd import runtime, specialize
 
-    name, idx, params = (RELAXED_CASES if kind == "relaxed" else RIGID_CASES)[key]
-    make = helpers.relaxed_model if kind == "relaxed" else helpers.rigid_model
-    model = make(models(name), idx, **params)
+    model, d_random = pc.contact_case(models, kind, key, 37, seed=5, dtype=np.float32)
 
     def run(d):
         g = to_gpu(model, d)
@@ -703,7 +630,7 @@ def test_mfma_cholesky_equals_the_vector_path_bitwise_gpu(models, kind, key, mon
             g = js.model.step(model, g)
         return g.state_block()
 
-    datas = (models.random_data(name, 37, seed=5, dtype=np.float32), helpers.standing_data(model, 37, seed=2, dtype=np.float32, noise=0.003))
+    datas = (d_random, helpers.standing_data(model, 37, seed=2, dtype=np.float32, noise=0.003))
     model.__dict__.pop("_device", None)
     default = [run(d) for d in datas]
     monkeypatch.setenv("JAXSIM_AMD_SPEC_EXTRA_FLAGS", "-DJXS_MFMA_CHOLESKY")
@@ -731,8 +658,7 @@ def test_fixed_base_rigid_contacts_match_oracle_gpu(reduced_qp, kind, base_veloc
     model), fixed-base forward dynamics, J nu / Jdot nu with the stored base velocity, and an impact that writes a
     base velocity into the state -- as rbda/contacts/rigid.py:222-446 and relaxed_rigid.py:330-420 do.  Three steps,
     fp64 1e-7 against the oracle; fp32 within 1e-3."""
-    model = helpers.fixed_cart_model(kind) if kind == "rigid" else helpers.fixed_cart_model(kind, mu=0.5)
-    d = helpers.fixed_cart_data(model, 41, seed=3, base_velocity=base_velocity)
+    model, d = pc.fixed_cart_case(kind, 41, base_velocity)
     ref, g = d, to_gpu(model, d)
     for _ in range(3):
         ref = oracle.step(model, ref)
@@ -740,7 +666,7 @@ def test_fixed_base_rigid_contacts_match_oracle_gpu(reduced_qp, kind, base_veloc
     assert helpers.rel_err(g.state_block(), helpers.odata_to_block(model, ref)) < 1e-7
     if kind == "rigid":
         assert np.abs(ref.base_linear_velocity).max() > 1e-8  # the impact moved the "fixed" base, as in the reference
-    d32 = helpers.fixed_cart_data(model, 41, seed=3, dtype=np.float32, base_velocity=base_velocity)
+    _, d32 = pc.fixed_cart_case(kind, 41, base_velocity, dtype=np.float32)
     out32 = js.model.step(model, to_gpu(model, d32)).state_block()
     err32 = helpers.rel_err(out32, helpers.odata_to_block(model, oracle.step(model, helpers.upcast(d32))))
     helpers.note(f"fixed_base_fp32/{kind}/{base_velocity}", err32)
@@ -753,18 +679,11 @@ def test_fifty_point_sphere_matches_oracle_gpu(models, reduced_qp, kind):
     (parsers/rod/utils.py:200-204), one lane per point in a 64-lane group.  RelaxedRigidContacts in fp64 (1e-9) and fp32.
     [round 4] RigidContacts in fp64 too (1e-7): round 3 refused it -- two 150 x 150 triangles of doubles, 182 KB, exceed
     the LDS of a CU -- the solve in the tree (jxs_rigid.inc ta_*) needs no triangle."""
-    make = helpers.rigid_model if kind == "rigid" else helpers.relaxed_model
-    model = make(models("sphere"), list(range(50)), **(dict(K=1e5) if kind == "rigid" else dict(mu=0.5)))
-    kw = dict(base_pos_bounds=((-1, -1, 0.04), (1, 1, 0.07)), base_rpy_bounds=((-3, -3, -3), (3, 3, 3)))
-    if kind == "relaxed":
-        d = oracle.random_model_data(model, batch_size=9, seed=6, **kw)
-        out = js.model.step(model, to_gpu(model, d))
-        assert helpers.rel_err(out.state_block(), helpers.odata_to_block(model, oracle.step(model, d))) < 1e-9
-    else:
-        d = oracle.random_model_data(model, batch_size=9, seed=6, **kw)
-        out = js.model.step(model, to_gpu(model, d))
-        assert helpers.rel_err(out.state_block(), helpers.odata_to_block(model, oracle.step(model, d))) < 1e-7
-    d32 = oracle.random_model_data(model, batch_size=9, seed=6, dtype=np.float32, **kw)
+    model = pc.sphere50_model(models, kind)
+    d = pc.sphere50_data(model, 9)
+    out = js.model.step(model, to_gpu(model, d))
+    assert helpers.rel_err(out.state_block(), helpers.odata_to_block(model, oracle.step(model, d))) < (1e-9 if kind == "relaxed" else 1e-7)
+    d32 = pc.sphere50_data(model, 9, np.float32)
     out32 = js.model.step(model, to_gpu(model, d32)).state_block()
     err32 = helpers.rel_err(out32, helpers.odata_to_block(model, oracle.step(model, helpers.upcast(d32))))
     helpers.note(f"sphere50_fp32/{kind}", err32)
@@ -795,9 +714,7 @@ def test_contact_solves_do_not_depend_on_wave_mates(models, kind, dtype):
 
 
 def test_rigid_tumbling_box_rollout_gpu(models, reduced_qp):
-    model = helpers.rigid_model(models("box"), [0, 1, 2, 3], K=1e5)
-    q = oracle.refmath.quaternion_from_euler_xyz(np.array([[0.3, 0.2, 0.1]]))
-    d = oracle.OracleData.build(model, base_position=[0, 0, 0.3], base_quaternion=q, base_linear_velocity=[0.5, 0, 0])
+    model, d = pc.tumbling_box(models, "rigid")
     out = js.model.rollout(model, to_gpu(model, d), 300).state_block()
     for _ in range(300):
         d = oracle.step(model, d)
@@ -948,10 +865,7 @@ def test_relaxed_contacts_with_200_points_gpu(dtype, tol):
     (parsers/rod/utils.py:200-204) -- with RelaxedRigidContacts: more points than lanes, chunks of 64 solved in the tree
     (jxs_rigid.inc relaxed_contact_forces_chunked).  VERDICT r4's done-criterion: fp32 <= 3e-3, fp64 <= 1e-9 against the
     oracle on the GPU; no solve discarded; the batch result does not depend on the batch."""
-    from jaxsim_amd import robots
-
-    base = ja.JaxSimModel.build_from_model_description(robots.anymal12_urdf(foot_shape="sphere"))
-    model = helpers.relaxed_model(base, range(200), mu=0.5)
+    model = helpers.relaxed_model(pc.quadruped_200(), range(200), mu=0.5)
     worst = 0.0
     for d in (oracle.random_model_data(model, batch_size=48, seed=1, dtype=dtype, base_pos_bounds=((-1, -1, 0.55), (1, 1, 0.68)), base_rpy_bounds=((-0.3, -0.3, -3), (0.3, 0.3, 3))),
               helpers.standing_data(model, 48, seed=1, dtype=dtype, noise=0.05)):  # fmt: skip
@@ -994,30 +908,11 @@ def test_gravity_compensated_step_equals_the_two_launch_loop(models, reduced_qp,
     assert helpers.rel_err(one, helpers.odata_to_block(model, ref)) < (1e-7 if dtype == np.float64 else 3e-3)
 
 
-# ---- RelaxedRigidContacts (rbda/contacts/relaxed_rigid.py; the model of the reference's own
-# test_simulation_step benchmark, tests/test_benchmark.py:142-152) ---------------------------------
-RELAXED_CASES = {
-    "box4": ("box", [0, 1, 2, 3], dict()),
-    "box8": ("box", list(range(8)), dict(mu=0.5)),
-    "anymal16": ("anymal", helpers.ANYMAL_FEET_16, dict(mu=0.5)),
-    "anymal4": ("anymal", helpers.ANYMAL_FEET_4, dict(time_constant=0.01, damping_coefficient=0.7, power=1.5)),
-    "chain9f6": ("chain9f", [0, 1, 2, 3, 8, 9], dict(mu=0.8, d_min=0.5, d_max=0.99, width=5e-3, midpoint=0.3)),
-    "serial12f": ("serial12f", list(range(16)), dict(mu=0.8, d_min=0.5, d_max=0.99, width=5e-3, midpoint=0.3)),
-    "icub16": ("icub16", list(range(16)), dict(mu=0.5)),
-    # [r4] the reference's DEFAULT parameters (mu = 0.005) on two links: solved in the tree in fp64 (jxs_pack.h)
-    "icub16d": ("icub16", list(range(16)), dict()),
-    # [round 5] parallel joint axes between the contact links
-    "planar_biped": ("planar_biped", list(range(16)), dict(mu=0.5)),
-    "planar10f": ("planar10f", list(range(16)), dict(mu=0.8, d_min=0.5, d_max=0.99, width=5e-3, midpoint=0.3)),
-}
-
-
+# ---- RelaxedRigidContacts (the cases: parity_cases.RELAXED_CASES) ---------------------------------
 @pytest.mark.parametrize("key", list(RELAXED_CASES))
 def test_relaxed_step_matches_oracle_gpu(models, key):
-    name, idx, params = RELAXED_CASES[key]
-    model = helpers.relaxed_model(models(name), idx, **params)
     N = 21  # not a multiple of the environments per wave
-    d = models.random_data(name, N, seed=5)
+    model, d = pc.relaxed_case(models, key, N, seed=5)
     tau, f = helpers.random_inputs(model, N, 7, np.float64)
     ref = oracle.step(model, d, link_forces=f, joint_force_references=tau)
     out = js.model.step(model, to_gpu(model, d), link_forces=f, joint_force_references=tau)
@@ -1047,9 +942,7 @@ def test_relaxed_defaults_in_fp32_stay_finite_gpu(models):
 def test_relaxed_step_fp32_gpu(models, key, tol):
     """fp32 against the fp64 oracle on the same inputs (host emulation of the same arithmetic: 5e-6 ..
     4e-5)."""
-    name, idx, params = RELAXED_CASES[key]
-    model = helpers.relaxed_model(models(name), idx, **params)
-    d = models.random_data(name, 40, seed=5, dtype=np.float32)
+    model, d = pc.relaxed_case(models, key, 40, seed=5, dtype=np.float32)
     ref = oracle.step(model, helpers.upcast(d))
     out = js.model.step(model, to_gpu(model, d))
     blk = out.state_block()
@@ -1076,7 +969,7 @@ def test_relaxed_bare_default_parameters_fp32_gpu(models):
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])
 def test_relaxed_box_settles_known_answer_gpu(models, dtype):
     """reference tests/test_simulations.py:295-346: x, y unchanged (atol 1e-5), z -> 0.05 (atol 1e-4)."""
-    model = helpers.relaxed_model(models("box"), [0, 1, 2, 3], build=dict(solver_options={"tol": 1e-3}))
+    model = pc.settling_box(models, "relaxed")
     d = oracle.OracleData.build(model, base_position=[0.0, 0.0, 0.2], velocity_representation=VelRepr.Inertial, dtype=dtype)
     out = js.model.rollout(model, to_gpu(model, d), 1000).state_block()
     assert abs(out[0, 0]) < 1e-5 and abs(out[1, 0]) < 1e-5
@@ -1093,11 +986,7 @@ def test_standing_on_every_sole_point_gpu(models, reduced_qp, kind, name, idx, d
     """Standing states with all 16 bottom points of the feet in contact (rank <= 18 of 48); the 32-point
     humanoid is BASELINE.json config 3's model with all its points enabled -- with RelaxedRigidContacts
     the analogue of the reference's own test_simulation_step benchmark (tests/test_benchmark.py:142-152)."""
-    if kind == "relaxed":
-        model = helpers.relaxed_model(models(name), idx, mu=0.5)
-    else:
-        model = helpers.rigid_model(models(name), idx, K=1e4, D=1e2)
-    d = helpers.standing_data(model, 21, seed=5, dtype=dtype, noise=0.003)
+    model, d = pc.standing_case(models, kind, name, idx, 21, dtype)
     ref = oracle.step(model, helpers.upcast(d))
     out = js.model.step(model, to_gpu(model, d)).state_block()
     assert out.dtype == dtype and np.isfinite(out).all()
@@ -1108,15 +997,14 @@ def test_standing_on_every_sole_point_gpu(models, reduced_qp, kind, name, idx, d
 def test_relaxed_rk4_step_matches_oracle_gpu(models, key):
     """RungeKutta4 with RelaxedRigidContacts (contact forces solved at each stage); the reference runs
     its relaxed-rigid test for every integrator (tests/test_simulations.py:295)."""
-    name, idx, params = RELAXED_CASES[key]
-    model = helpers.with_params(helpers.relaxed_model(models(name), idx, **params), integrator=ja.IntegratorType.RungeKutta4)
     N = 21
-    d = models.random_data(name, N, seed=5)
+    model, d = pc.relaxed_case(models, key, N, seed=5)
+    model = helpers.with_params(model, integrator=ja.IntegratorType.RungeKutta4)
     tau, f = helpers.random_inputs(model, N, 7, np.float64)
     ref = oracle.step(model, d, link_forces=f, joint_force_references=tau)
     out = js.model.step(model, to_gpu(model, d), link_forces=f, joint_force_references=tau)
     assert helpers.rel_err(out.state_block(), helpers.odata_to_block(model, ref)) < 1e-10
-    d32 = models.random_data(name, N, seed=5, dtype=np.float32)
+    _, d32 = pc.relaxed_case(models, key, N, seed=5, dtype=np.float32)
     out32 = js.model.step(model, to_gpu(model, d32)).state_block()
     ref32 = oracle.step(model, helpers.upcast(d32))
     assert out32.dtype == np.float32 and helpers.rel_err(out32, helpers.odata_to_block(model, ref32)) < 5e-4
@@ -1125,8 +1013,7 @@ def test_relaxed_rk4_step_matches_oracle_gpu(models, key):
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])
 def test_relaxed_rk4_box_settles_known_answer_gpu(models, dtype):
     """reference tests/test_simulations.py:295-346 with integrator = RungeKutta4."""
-    model = helpers.relaxed_model(models("box"), [0, 1, 2, 3], build=dict(solver_options={"tol": 1e-3}))
-    model = helpers.with_params(model, integrator=ja.IntegratorType.RungeKutta4)
+    model = pc.settling_box(models, "relaxed", ja.IntegratorType.RungeKutta4)
     d = oracle.OracleData.build(model, base_position=[0.0, 0.0, 0.2], velocity_representation=VelRepr.Inertial, dtype=dtype)
     out = js.model.rollout(model, to_gpu(model, d), 1000).state_block()
     assert abs(out[0, 0]) < 1e-5 and abs(out[1, 0]) < 1e-5
@@ -1134,9 +1021,7 @@ def test_relaxed_rk4_box_settles_known_answer_gpu(models, dtype):
 
 
 def test_relaxed_tumbling_box_rollout_gpu(models):
-    model = helpers.relaxed_model(models("box"), [0, 1, 2, 3], mu=0.5)
-    q = oracle.refmath.quaternion_from_euler_xyz(np.array([[0.3, 0.2, 0.1]]))
-    d = oracle.OracleData.build(model, base_position=[0, 0, 0.3], base_quaternion=q, base_linear_velocity=[0.5, 0, 0])
+    model, d = pc.tumbling_box(models, "relaxed")
     out = js.model.rollout(model, to_gpu(model, d), 300).state_block()
     for _ in range(300):
         d = oracle.step(model, d)
@@ -1165,10 +1050,8 @@ def test_relaxed_estimated_parameters_and_large_batch(models):
 
 @pytest.mark.parametrize("name", ["box", "anymal"])
 def test_gpu_golden_relaxed(models, name):
-    import test_golden as tg
-
-    g = tg.load(f"relaxed_{name}")
-    model = tg._relaxed_model(models, name, g)
+    g = pc.load(f"relaxed_{name}")
+    model = pc.relaxed_golden_model(models, name, g)
     data = js.data.JaxSimModelData.from_state_block(model, g["state"], ja.VelRepr.Mixed)
     out = js.model.step(model, data, link_forces=g["link_forces"], joint_force_references=g["tau"])
     assert helpers.rel_err(out.state_block(), g["step"]) < 1e-10
@@ -1202,20 +1085,16 @@ def test_step_with_references_object(models, rep):
 
 @pytest.mark.parametrize("tag", ["relaxed_rk4_anymal", "relaxed_rk4fast_anymal", "rigid_rk4_box", "rigid_rk4fast_box"])
 def test_gpu_golden_rigid_models_integrators(models, tag):
-    import test_golden as tg
-
-    g = tg.load(tag)
-    model = tg._integrator_golden_model(models, tag, g)
+    g = pc.load(tag)
+    model = pc.integrator_golden_model(models, tag, g)
     data = js.data.JaxSimModelData.from_state_block(model, g["state"], ja.VelRepr.Mixed)
     out = js.model.step(model, data, link_forces=g["link_forces"], joint_force_references=g["tau"])
-    assert helpers.rel_err(out.state_block(), g["step"]) < (1e-10 if tg.INTEGRATOR_GOLDEN[tag][0] == "relaxed" else 1e-7)
+    assert helpers.rel_err(out.state_block(), g["step"]) < (1e-10 if pc.INTEGRATOR_GOLDEN[tag][0] == "relaxed" else 1e-7)
 
 
 @pytest.mark.parametrize("name", ["cartpole", "chain9f", "icub"])
 def test_gpu_golden_rk4(models, name):
-    import test_golden as tg
-
-    g, model = tg.load(f"rk4_{name}"), tg._rk4_model(models, name)
+    g, model = pc.load(f"rk4_{name}"), pc.rk4_golden_model(models, name)
     N = g["state"].shape[1]
     data = js.data.JaxSimModelData.from_state_block(model, g["state"], ja.VelRepr.Mixed)
     out = js.model.step(model, data, link_forces=g["link_forces"], joint_force_references=g["tau"])
@@ -1228,10 +1107,8 @@ def test_gpu_golden_rk4(models, name):
 
 @pytest.mark.parametrize("name", ["box", "anymal"])
 def test_gpu_golden_rigid(models, name):
-    import test_golden as tg
-
-    g = tg.load(f"rigid_{name}")
-    model = tg._rigid_model(models, name, g)
+    g = pc.load(f"rigid_{name}")
+    model = pc.rigid_golden_model(models, name, g)
     data = js.data.JaxSimModelData.from_state_block(model, g["state"], ja.VelRepr.Mixed)
     out = js.model.step(model, data, link_forces=g["link_forces"], joint_force_references=g["tau"])
     assert helpers.rel_err(out.state_block(), g["step"]) < 1e-7
@@ -1566,10 +1443,8 @@ def test_rigid_step_matches_unreduced_statement_gpu(models, key):
     from oracle import refrigid
 
     assert refrigid.REDUCED_QP is False
-    name, idx, params = RIGID_CASES[key]
-    model = helpers.rigid_model(models(name), idx, build=dict(solver_options={"solver_tol": 1e-10}), **params)
     N = 21
-    d = models.random_data(name, N, seed=5)
+    model, d = pc.rigid_case(models, key, N, seed=5, build=dict(solver_options={"solver_tol": 1e-10}))
     tau, f = helpers.random_inputs(model, N, 7, np.float64)
     ref = oracle.step(model, d, link_forces=f, joint_force_references=tau)
     out = js.model.step(model, to_gpu(model, d), link_forces=f, joint_force_references=tau)
@@ -1577,9 +1452,6 @@ def test_rigid_step_matches_unreduced_statement_gpu(models, key):
 
 
 # ---- Jacobian kernel + host assembly (rbda/jacobian.py:128-339, api/model.py:925-1228) ---------------------
-REPS = [VelRepr.Inertial, VelRepr.Body, VelRepr.Mixed]
-
-
 @pytest.mark.parametrize("name", ["cartpole", "chain9f", "anymal", "icub"])
 def test_jacobian_full_kernel_gpu(models, name):
     from oracle import refrigid
@@ -1747,30 +1619,7 @@ def test_a_non_finite_environment_does_not_touch_its_neighbours(models, case, dt
 # SURVEY section 8(a) rows E and I as callable entries (jxs_system_dynamics, jxs_link_contact_forces; kernel modes MODE_DYN /
 # MODE_DYN_RIGID).  Reference: src/jaxsim/api/ode.py:16-225, src/jaxsim/api/contact.py:514-603 -- what the reference's
 # contact-model benchmarks time (tests/test_benchmark.py:103-139).
-def _dyn_err(a, ref, dtype):
-    """fp64: helpers.rel_err element by element.  fp32: the worst element error of an environment relative to the largest
-    entry of that environment's reference (at least 1) -- see tests/test_emulation_parity.py helpers_dyn_err."""
-    a, ref = np.asarray(a, np.float64), np.asarray(ref, np.float64)
-    if np.dtype(dtype) == np.float64:
-        return helpers.rel_err(a, ref)
-    a, ref = a.reshape(a.shape[0], -1), ref.reshape(ref.shape[0], -1)
-    return float(np.max(np.abs(a - ref).max(axis=1) / np.maximum(1.0, np.abs(ref).max(axis=1)))) if a.size else 0.0
-
-
-def _oracle_link_contact_forces(model, d, tau, f):
-    if oracle.refstep.is_rigid_contact_model(model):
-        from oracle import refrigid
-
-        return refrigid.link_contact_forces(model, d, link_forces=f, joint_torques=tau)[0]
-    if oracle.refstep.is_relaxed_rigid_contact_model(model):
-        from oracle import refrelaxed
-
-        return refrelaxed.link_contact_forces(model, d, link_forces=f, joint_torques=tau)[0]
-    if model.kin_dyn_parameters.number_of_collidable_points() == 0:
-        return np.zeros((d.batch_size, model.number_of_links(), 6))
-    return oracle.refstep.link_contact_forces(model, d)[0]
-
-
+# (the error metric and the oracle's link wrenches: parity_cases.dyn_err / link_contact_forces)
 def _check_dynamics(model, d, tau, f, dtype, tol):
     """system_dynamics (every key), link_contact_forces and system_acceleration of the device against the oracle."""
     N = d.batch_size
@@ -1784,20 +1633,20 @@ def _check_dynamics(model, d, tau, f, dtype, tol):
     got = js.ode.system_dynamics(model, g, link_forces=f, joint_torques=tau)
     for key in ("base_position", "base_quaternion", "joint_positions", "base_linear_velocity", "base_angular_velocity", "joint_velocities"):
         assert np.asarray(got[key]).dtype == dtype
-        assert _dyn_err(got[key], ref[key], dtype) < tol, key
+        assert pc.dyn_err(got[key], ref[key], dtype) < tol, key
     if oracle.refstep.is_rigid_contact_model(model) or oracle.refstep.is_relaxed_rigid_contact_model(model):
         assert got["contact_state"] == {}
     elif model.kin_dyn_parameters.number_of_collidable_points() > 0:
-        assert _dyn_err(got["contact_state"]["tangential_deformation"], ref["tangential_deformation"], dtype) < tol
+        assert pc.dyn_err(got["contact_state"]["tangential_deformation"], ref["tangential_deformation"], dtype) < tol
     # --- link_contact_forces: link forces in the data's representation (rigid models; SoftContacts ignores the inputs)
-    ref_W = _oracle_link_contact_forces(model, d64, tau64, f64)
+    ref_W = pc.link_contact_forces(model, d64, tau64, f64)
     W, aux = js.contact.link_contact_forces(model, g, link_forces=f, joint_torques=tau)
     assert np.asarray(W).shape == (N, model.number_of_links(), 6)
-    assert _dyn_err(W, ref_W, dtype) < tol
+    assert pc.dyn_err(W, ref_W, dtype) < tol
     # --- system_acceleration in the data's representation, as written (oracle.refstep.system_acceleration_active)
     vd, sdd, md = oracle.refstep.system_acceleration_active(model, d64, link_forces=f64, joint_torques=tau64)
     gvd, gsdd, gcs = js.ode.system_acceleration(model, g, link_forces=f, joint_torques=tau)
-    assert _dyn_err(np.concatenate([np.asarray(gvd), np.asarray(gsdd)], -1), np.concatenate([vd, sdd], -1), dtype) < tol
+    assert pc.dyn_err(np.concatenate([np.asarray(gvd), np.asarray(gsdd)], -1), np.concatenate([vd, sdd], -1), dtype) < tol
     return ref_W, aux, gcs, md
 
 
@@ -1822,8 +1671,8 @@ def test_system_dynamics_matches_oracle_gpu(models, name, dtype, rep):
     ref_W, aux, gcs, md = _check_dynamics(model, d, tau, f, dtype, tol)
     if name in models.contact_z:
         assert np.abs(ref_W).max() > 1.0  # contacts really act in this sample
-        assert _dyn_err(aux["m_dot"], md, dtype) < tol
-        assert _dyn_err(gcs["tangential_deformation"], md, dtype) < tol
+        assert pc.dyn_err(aux["m_dot"], md, dtype) < tol
+        assert pc.dyn_err(gcs["tangential_deformation"], md, dtype) < tol
 
 
 def test_system_dynamics_without_inputs_and_one_environment_gpu(models):
@@ -1869,10 +1718,8 @@ DYN_RIGID_KEYS = ["box4", "anymal16", "anymal4", "icub8"]
 @pytest.mark.parametrize("key", DYN_RIGID_KEYS)
 @pytest.mark.parametrize("rep", [VelRepr.Inertial, VelRepr.Mixed])
 def test_rigid_system_dynamics_matches_oracle_gpu(models, reduced_qp, key, rep):
-    name, idx, params = RIGID_CASES[key]
-    model = helpers.rigid_model(models(name), idx, **params)
     N = 21
-    d = models.random_data(name, N, seed=5, rep=rep)
+    model, d = pc.rigid_case(models, key, N, seed=5, rep=rep)
     tau, f = helpers.random_inputs(model, N, 7, np.float64)
     ref_W, aux, gcs, _ = _check_dynamics(model, d, tau, f, np.float64, 1e-6)  # (accelerations: the step's 1e-7 gate sees dt x these)
     assert np.abs(ref_W).max() > 1.0 and aux == {} and gcs == {}
@@ -1880,9 +1727,7 @@ def test_rigid_system_dynamics_matches_oracle_gpu(models, reduced_qp, key, rep):
 
 @pytest.mark.parametrize("key", ["anymal4", "icub8", "anymal16"])
 def test_rigid_system_dynamics_fp32_gpu(models, reduced_qp, key):
-    name, idx, params = RIGID_CASES[key]
-    model = helpers.rigid_model(models(name), idx, **params)
-    d = models.random_data(name, 40, seed=5, dtype=np.float32, rep=VelRepr.Inertial)
+    model, d = pc.rigid_case(models, key, 40, seed=5, dtype=np.float32, rep=VelRepr.Inertial)
     tau, f = helpers.random_inputs(model, 40, 7, np.float32)
     _check_dynamics(model, d, tau, f, np.float32, 3e-3)
 
@@ -1893,10 +1738,8 @@ DYN_RELAXED_KEYS = ["box8", "anymal16", "icub16"]
 @pytest.mark.parametrize("key", DYN_RELAXED_KEYS)
 @pytest.mark.parametrize("rep", [VelRepr.Inertial, VelRepr.Body])
 def test_relaxed_system_dynamics_matches_oracle_gpu(models, key, rep):
-    name, idx, params = RELAXED_CASES[key]
-    model = helpers.relaxed_model(models(name), idx, **params)
     N = 21
-    d = models.random_data(name, N, seed=5, rep=rep)
+    model, d = pc.relaxed_case(models, key, N, seed=5, rep=rep)
     tau, f = helpers.random_inputs(model, N, 7, np.float64)
     ref_W, aux, gcs, _ = _check_dynamics(model, d, tau, f, np.float64, 1e-8)
     assert np.abs(ref_W).max() > 1.0 and aux == {} and gcs == {}
@@ -1904,9 +1747,7 @@ def test_relaxed_system_dynamics_matches_oracle_gpu(models, key, rep):
 
 @pytest.mark.parametrize("key", ["anymal16", "icub16"])
 def test_relaxed_system_dynamics_fp32_gpu(models, key):
-    name, idx, params = RELAXED_CASES[key]
-    model = helpers.relaxed_model(models(name), idx, **params)
-    d = models.random_data(name, 40, seed=5, dtype=np.float32, rep=VelRepr.Inertial)
+    model, d = pc.relaxed_case(models, key, 40, seed=5, dtype=np.float32, rep=VelRepr.Inertial)
     tau, f = helpers.random_inputs(model, 40, 7, np.float32)
     _check_dynamics(model, d, tau, f, np.float32, 2e-3)
 
@@ -1950,19 +1791,10 @@ def test_link_forces_from_contact_forces_host(models):
 
 
 # ---- [round 6] height-field terrain (the generic finite-difference normal, terrain.py:40-62) --
-def _sine_field(extent=4.0, spacing=0.05, amp=0.04):
-    """(product terrain, oracle terrain of the same grid): see tests/test_emulation_parity.py _sine_field."""
-    from oracle import refterrain
-
-    fn = lambda x, y: amp * (np.sin(2.1 * x + 0.3) * np.cos(1.7 * y) + 0.3 * np.sin(3.3 * y))  # noqa: E731
-    t = ja.HeightFieldTerrain.from_function(fn, x_range=(-extent, extent), y_range=(-extent, extent), spacing=spacing)
-    return t, refterrain.GridTerrain(np.array(t._heights), t._origin, t._spacing, t.delta)
-
-
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])
 @pytest.mark.parametrize("name", ["box", "icub"])
 def test_height_field_terrain_soft_gpu(models, name, dtype):
-    t, g = _sine_field()
+    t, g, _ = pc.sine_field()
     model = helpers.with_params(models(name), terrain=t)
     N = 70
     d = models.random_data(name, N, seed=23, dtype=dtype)
@@ -1981,11 +1813,9 @@ def test_height_field_terrain_soft_gpu(models, name, dtype):
 
 @pytest.mark.parametrize("kind,key", [("rigid", "box4"), ("rigid", "anymal4"), ("relaxed", "box8"), ("relaxed", "anymal16")])
 def test_height_field_terrain_rigid_models_gpu(models, reduced_qp, kind, key):
-    t, g = _sine_field()
-    name, idx, params = (RIGID_CASES if kind == "rigid" else RELAXED_CASES)[key]
-    base = (helpers.rigid_model if kind == "rigid" else helpers.relaxed_model)(models(name), idx, **params)
+    t, g, _ = pc.sine_field()
+    base, d = pc.contact_case(models, kind, key, 24, seed=5)
     model = helpers.with_params(base, terrain=t)
-    d = models.random_data(name, 24, seed=5)
     ref = oracle.step(helpers.with_params(model, terrain=g), d)
     out = js.model.step(model, to_gpu(model, d))
     assert helpers.rel_err(out.state_block(), helpers.odata_to_block(model, ref)) < (1e-7 if kind == "rigid" else 1e-9)
@@ -2006,10 +1836,6 @@ def test_height_field_that_is_a_plane_equals_plane_terrain_gpu(models):
 
 
 # ---- [round 6] links with more than six children (VERDICT r5 missing 3: kMaxChildren 6 -> 12) --------------------------
-OCTOPOD_FEET_4 = [0, 8, 16, 24]
-OCTOPOD_FEET_16 = [8 * f + c for f in range(4) for c in range(4)]
-
-
 @pytest.mark.parametrize("name", ["octopod", "hub12"])
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])
 def test_links_with_more_than_six_children_gpu(models, name, dtype):
@@ -2052,12 +1878,8 @@ def test_links_with_more_than_six_children_gpu(models, name, dtype):
                                                 ("relaxed", OCTOPOD_FEET_16, np.float64, 1e-10), ("rigid", OCTOPOD_FEET_4, np.float32, 3e-3),
                                                 ("relaxed", OCTOPOD_FEET_16, np.float32, 1e-3)])
 def test_octopod_with_the_rigid_contact_models_gpu(models, reduced_qp, kind, idx, dtype, tol):
-    if kind == "rigid":
-        model = helpers.rigid_model(models("octopod"), idx, K=1e4, D=1e2)
-    else:
-        model = helpers.relaxed_model(models("octopod"), idx, mu=0.5)
     N = 24
-    d = models.random_data("octopod", N, seed=5, dtype=dtype)
+    model, d = pc.octopod_case(models, kind, idx, N, dtype)
     tau, f = helpers.random_inputs(model, N, 7, dtype)
     ref = oracle.step(model, helpers.upcast(d), link_forces=f.astype(np.float64), joint_force_references=tau.astype(np.float64))
     out = js.model.step(model, to_gpu(model, d), link_forces=f, joint_force_references=tau)

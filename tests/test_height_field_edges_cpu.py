@@ -22,7 +22,7 @@ import height_field_cases as hfc
 import helpers
 import oracle
 from oracle import VelRepr
-from test_emulation_parity import RELAXED_CASES, RIGID_CASES, _dyn_reference, helpers_dyn_err, reduced_qp  # noqa: F401
+from parity_cases import RELAXED_CASES, RIGID_CASES, dyn_err, dyn_reference, reduced_qp  # noqa: F401
 
 
 def _block(model, d):
@@ -59,12 +59,12 @@ def test_soft_step_and_dynamics_on_the_edge_field(models, name, dtype):
     assert hfc.measured(f"emul step {name} {np.dtype(dtype).name}", helpers.rel_err(out, _block(model, ref)), tol) < tol
     # the derivative and the link wrenches of system_dynamics see the same grid (gate rule of test_height_field_terrain_soft)
     d_in = dataclasses.replace(helpers.upcast(d, model), velocity_representation=VelRepr.Inertial)
-    ref_blk, ref_W = _dyn_reference(model_ref, d_in, None, None)
+    ref_blk, ref_W = dyn_reference(model_ref, d_in, None, None)
     xdot, W = eb.run(model, eb.MODE_DYN, _block(model, d))
     tol_dyn = max(tol, 1e-3 if dtype == np.float32 else 0)
-    assert hfc.measured(f"emul xdot {name} {np.dtype(dtype).name}", helpers_dyn_err(xdot, ref_blk, dtype), tol_dyn) < tol_dyn
+    assert hfc.measured(f"emul xdot {name} {np.dtype(dtype).name}", dyn_err(xdot, ref_blk, dtype, env_axis=-1), tol_dyn) < tol_dyn
     ref_W = ref_W.reshape(d.batch_size, -1).T
-    assert hfc.measured(f"emul wrenches {name} {np.dtype(dtype).name}", helpers_dyn_err(W, ref_W, dtype), tol_dyn) < tol_dyn
+    assert hfc.measured(f"emul wrenches {name} {np.dtype(dtype).name}", dyn_err(W, ref_W, dtype, env_axis=-1), tol_dyn) < tol_dyn
     assert np.abs(ref_W).max() > 1.0
 
 

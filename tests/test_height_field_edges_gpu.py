@@ -13,7 +13,7 @@ import pytest
 
 import height_field_cases as hfc
 import helpers
-import jaxsim_amd as ja
+from helpers import REP, to_gpu
 import jaxsim_amd.api as js
 import oracle
 from jaxsim_amd import _lib, runtime, specialize
@@ -22,10 +22,10 @@ from jaxsim_amd.api import ode as _ode
 from jaxsim_amd.runtime import DeviceArray
 from jaxsim_amd.state import StateLayout, untile_block
 from oracle import VelRepr
+from parity_cases import reduced_qp  # noqa: F401  (a fixture)
 
 pytestmark = pytest.mark.gpu
 
-REP = {VelRepr.Inertial: ja.VelRepr.Inertial, VelRepr.Body: ja.VelRepr.Body, VelRepr.Mixed: ja.VelRepr.Mixed}
 DYN_KEYS = ("base_position", "base_quaternion", "joint_positions", "base_linear_velocity", "base_angular_velocity", "joint_velocities")
 MDOT_N = 37  # no multiple of any tile: the last tile of the copy is ragged
 # (name, enabled points or None for all, RigidContacts parameters or None for SoftContacts, precisions)
@@ -36,19 +36,6 @@ MDOT_CASES = {
     "anymal4_rigid": ("anymal", helpers.ANYMAL_FEET_4, dict(), (np.float64,)),
 }
 MDOT_PARAMS = [(key, dt) for key, case in MDOT_CASES.items() for dt in case[3]]
-
-
-@pytest.fixture()
-def reduced_qp():
-    from oracle import refrigid
-
-    refrigid.REDUCED_QP = True
-    yield refrigid
-    refrigid.REDUCED_QP = False
-
-
-def to_gpu(model, d: oracle.OracleData) -> js.data.JaxSimModelData:
-    return js.data.JaxSimModelData.from_state_block(model, helpers.odata_to_block(model, d), REP[d.velocity_representation])
 
 
 def mdot_model(zoo, key):

@@ -551,3 +551,33 @@ def test_the_names_of_api_data_are_one_object_wherever_they_are_imported_from():
     # ... and env_specs stands below data: it imports nothing of it
     imports = [n for n in ast.walk(ast.parse(pathlib.Path(env_specs.__file__).read_text())) if isinstance(n, (ast.Import, ast.ImportFrom))]
     assert imports and not any("data" in (getattr(n, "module", None) or "").split(".") or any(a.name.split(".")[-1] == "data" for a in n.names) for n in imports)
+
+
+def test_no_test_module_is_imported_as_a_library():
+    """Shared cases and helpers live in tests/parity_cases.py, tests/helpers.py, the ``*_cases.py`` / ``*_ref.py`` /
+    ``env_*_support.py`` modules: no test module, tool, bench.py or the build step imports a ``test_*`` module -- by an
+    import statement or by naming one to ``importlib.import_module`` -- except where the test module is the SUBJECT."""
+    import ast
+    import pathlib
+    import re
+
+    root = pathlib.Path(__file__).resolve().parent.parent
+    allowed = {("__graft_entry__.py", m) for m in ("test_centroidal_gpu", "test_frames_gpu", "test_env_contact_gpu", "test_coriolis_gpu",
+                                                   "test_fd_crb_gpu", "test_query_modes_trees_gpu")}  # their gpu_models(zoo): what build() pre-builds
+    # the manifest checks: every kernel the GPU module asks for is recorded
+    allowed |= {("tests/test_soft_regimes_cpu.py", "test_soft_regimes_gpu"), ("tests/test_height_field_edges_cpu.py", "test_height_field_edges_gpu")}
+    files = sorted(root.glob("tests/*.py")) + sorted(root.glob("tools/**/*.py")) + [root / "bench.py", root / "__graft_entry__.py"]
+    found = set()
+    for path in files:
+        tree, rel = ast.parse(path.read_text()), path.relative_to(root).as_posix()
+        nodes = list(ast.walk(tree))
+        for node in nodes:
+            if isinstance(node, ast.Import):
+                found |= {(rel, a.name.split(".")[0]) for a in node.names}
+            elif isinstance(node, ast.ImportFrom):
+                found |= {(rel, (node.module or "").split(".")[0])} | ({(rel, a.name) for a in node.names} if not node.module else set())
+        if any(isinstance(n, ast.Call) and getattr(n.func, "attr", getattr(n.func, "id", "")) in ("import_module", "__import__") for n in nodes):
+            found |= {(rel, n.value) for n in nodes if isinstance(n, ast.Constant) and isinstance(n.value, str) and re.fullmatch(r"test_\w+", n.value)}
+    offenders = sorted((rel, mod) for rel, mod in found if mod.startswith("test_") and (rel, mod) not in allowed)
+    assert not offenders, f"test modules imported as libraries: {offenders}"
+    assert allowed <= found  # (the allow-list names only what exists)

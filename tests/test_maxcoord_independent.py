@@ -19,61 +19,8 @@ import helpers
 import jaxsim_amd as ja
 import maxcoord
 import oracle
-from jaxsim_amd import robots
 from oracle import VelRepr
-
-TEXTS = {
-    "cartpole": lambda: robots.cartpole_urdf(),
-    "pendulum": lambda: robots.single_pendulum_urdf(),
-    "double_pendulum": lambda: robots.double_pendulum_urdf(),
-    "chain5": lambda: robots.chain_urdf(5, fixed_base=True, seed=1),
-    "chain9f": lambda: robots.chain_urdf(9, fixed_base=False, seed=2),
-    "box": lambda: robots.box_urdf(),
-    "anymal": lambda: robots.anymal12_urdf(),
-    "icub": lambda: robots.icub23_urdf(),
-    "octopod": lambda: robots.hub_urdf(8, 2, foot_boxes=4, seed=1),
-    "lumped7f": lambda: robots.lumped_tree_urdf(7, seed=0),
-    "lumped12f": lambda: robots.lumped_tree_urdf(12, seed=2),
-    "lumped5": lambda: robots.lumped_tree_urdf(5, seed=1, fixed_base=True),
-}
-OFFSET_BASE = ("pendulum", "chain5", "double_pendulum")  # fixed bases placed off the world origin: no link wrenches (quirk 12)
-_MODELS = {}
-
-
-def case(name, N, seed, dtype=np.float64):
-    if name not in _MODELS:
-        text = TEXTS[name]()
-        _MODELS[name] = (text, ja.JaxSimModel.build_from_model_description(text))
-    text, model = _MODELS[name]
-    d = oracle.random_model_data(model, batch_size=N, seed=seed, dtype=dtype, velocity_representation=VelRepr.Mixed)
-    if not model.floating_base():  # ABA keeps the base of a fixed-base model at rest (rbda/aba.py:109-121)
-        d.base_linear_velocity[:] = 0
-        d.base_angular_velocity[:] = 0
-    rng = np.random.default_rng(seed + 1)
-    tau = rng.uniform(-3, 3, size=(N, model.dofs())).astype(dtype)
-    f = rng.uniform(-5, 5, size=(N, model.number_of_links(), 6)).astype(dtype)
-    if name in OFFSET_BASE:
-        f[:] = 0
-    return text, model, d, tau, f
-
-
-def truth(text, model, d, tau, f):
-    """(base acceleration in MIXED representation [N, 6], joint accelerations [N, n] in the model's joint order) from
-    tests/maxcoord.py; the inputs are read in float64 whatever the dtype of the state."""
-    jn, lnm = model.joint_names(), model.link_names()
-    N = d.base_position.shape[0]
-    vd, sdd = np.zeros((N, 6)), np.zeros((N, len(jn)))
-    bv = d.base_velocity(VelRepr.Mixed).astype(np.float64)  # (the data object STORES the inertial-fixed velocity, api/data.py:151-156)
-    for e in range(N):
-        ba, acc = maxcoord.forward_dynamics(
-            text, base_position=d.base_position[e].astype(np.float64), base_quaternion=d.base_quaternion[e].astype(np.float64),
-            base_linear_velocity=bv[e, :3], base_angular_velocity=bv[e, 3:],
-            joint_positions=dict(zip(jn, d.joint_positions[e].astype(np.float64))), joint_velocities=dict(zip(jn, d.joint_velocities[e].astype(np.float64))),
-            joint_forces=dict(zip(jn, tau[e].astype(np.float64))),
-            link_wrenches={n: (f[e, i, :3].astype(np.float64), f[e, i, 3:].astype(np.float64)) for i, n in enumerate(lnm)}, gravity=model.gravity)  # fmt: skip
-        vd[e] = ba
-        sdd[e] = [acc[n] for n in jn]
-    return vd, sdd
+from parity_cases import MAXCOORD_TEXTS, maxcoord_case, maxcoord_truth
 
 
 def mixed_state_is_stored(d):
@@ -116,11 +63,11 @@ def test_free_rigid_body_known_answer():
     np.testing.assert_allclose(ba[:3], np.array([0, 0, -9.81]) + np.cross(alpha, r) + np.cross(w, np.cross(w, r)), atol=1e-13)
 
 
-@pytest.mark.parametrize("name", list(TEXTS))
+@pytest.mark.parametrize("name", list(MAXCOORD_TEXTS))
 def test_oracle_forward_dynamics_equals_maximal_coordinates(name):
-    text, model, d, tau, f = case(name, 4, seed=3)
+    text, model, d, tau, f = maxcoord_case(name, 4, seed=3)
     mixed_state_is_stored(d)
-    vd, sdd = truth(text, model, d, tau, f)
+    vd, sdd = maxcoord_truth(text, model, d, tau, f)
     ovd, osdd = oracle.forward_dynamics_aba(model, d, joint_forces=tau, link_forces=f)
     assert rel(osdd, sdd) < 1e-10
     if model.floating_base():
@@ -130,7 +77,7 @@ def test_oracle_forward_dynamics_equals_maximal_coordinates(name):
 def test_lumping_is_what_the_comparison_sees():
     """The lumped trees really exercise the rule: the product's table has 7 links where the URDF has 7 + payloads, and the
     lumped mass is the sum."""
-    text, model = TEXTS["lumped7f"](), None
+    text, model = MAXCOORD_TEXTS["lumped7f"](), None
     U = maxcoord.Urdf(text)
     model = ja.JaxSimModel.build_from_model_description(text)
     n_bodies = sum(1 for rec in U.links.values() if rec["mass"] > 0)
@@ -138,15 +85,15 @@ def test_lumping_is_what_the_comparison_sees():
     np.testing.assert_allclose(np.sum(model.kin_dyn_parameters.link_mass), sum(rec["mass"] for rec in U.links.values()), rtol=1e-12)
 
 
-@pytest.mark.parametrize("name", list(TEXTS))
+@pytest.mark.parametrize("name", list(MAXCOORD_TEXTS))
 @pytest.mark.parametrize("dtype,tol", [(np.float64, 1e-10), (np.float32, 2e-4)])
 def test_kernel_core_equals_maximal_coordinates(name, dtype, tol):
     """The kernel core (host emulation of the HIP kernels' source) through its raw interface: inertial-fixed base
     acceleration out, converted to mixed by hand here -- pddot_B = vdot_O + wdot x p_B + w x pdot_B."""
     import emul_binding as eb
 
-    text, model, d, tau, f = case(name, 4, seed=3, dtype=dtype)
-    vd, sdd = truth(text, model, d, tau, f)
+    text, model, d, tau, f = maxcoord_case(name, 4, seed=3, dtype=dtype)
+    vd, sdd = maxcoord_truth(text, model, d, tau, f)
     out = eb.run(model, eb.MODE_FD, helpers.odata_to_block(model, d), tau=tau.T, link_forces=f.reshape(4, -1).T, force_repr=2).T.astype(np.float64)
     assert rel(out[:, 6:], sdd) < tol
     if model.floating_base():
@@ -157,15 +104,15 @@ def test_kernel_core_equals_maximal_coordinates(name, dtype, tol):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("name", list(TEXTS))
+@pytest.mark.parametrize("name", list(MAXCOORD_TEXTS))
 @pytest.mark.parametrize("dtype,tol", [(np.float64, 1e-10), (np.float32, 2e-4)])
 def test_hip_kernels_equal_maximal_coordinates_gpu(name, dtype, tol):
     """``js.model.forward_dynamics_aba`` on the device (C-ABI ``jxs_forward_dynamics_aba``), mixed representation in and out."""
     import jaxsim_amd.api as js
 
     N = 37
-    text, model, d, tau, f = case(name, N, seed=4, dtype=dtype)
-    vd, sdd = truth(text, model, d, tau, f)
+    text, model, d, tau, f = maxcoord_case(name, N, seed=4, dtype=dtype)
+    vd, sdd = maxcoord_truth(text, model, d, tau, f)
     g = js.data.JaxSimModelData.from_state_block(model, helpers.odata_to_block(model, d), ja.VelRepr.Mixed)
     gvd, gsdd = js.model.forward_dynamics_aba(model, g, joint_forces=tau, link_forces=f)
     assert rel(gsdd, sdd) < tol

@@ -11,21 +11,15 @@ import numpy as np
 import pytest
 
 import helpers
-import jaxsim_amd as ja
+from helpers import to_gpu
 import jaxsim_amd.api as js
 import oracle
 import soft_regime_cases as src
 from jaxsim_amd import specialize
-from oracle import VelRepr
 
 pytestmark = pytest.mark.gpu
 
-REP = {VelRepr.Inertial: ja.VelRepr.Inertial, VelRepr.Body: ja.VelRepr.Body, VelRepr.Mixed: ja.VelRepr.Mixed}
 DYN_KEYS = ("base_position", "base_quaternion", "joint_positions", "base_linear_velocity", "base_angular_velocity", "joint_velocities")
-
-
-def to_gpu(model, d: oracle.OracleData) -> js.data.JaxSimModelData:
-    return js.data.JaxSimModelData.from_state_block(model, helpers.odata_to_block(model, d), REP[d.velocity_representation])
 
 
 def launches(zoo):

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""fp32 error of one GPU step against the fp64 oracle, per model (the states of tests/test_gpu_parity.py):
+"""fp32 error of one GPU step against the fp64 oracle, per model (the states of tests/test_gpu_parity.py, the contact cases of tests/parity_cases.py):
 worst element and distribution over the environments.  Next to it the reference formulation evaluated in fp32
 (the oracle run with float32 arrays).   python tools/fp32_error_gpu.py [N]"""
 import os
@@ -29,8 +29,8 @@ for name in ["box", "sphere", "pendulum", "double_pendulum", "cartpole", "chain5
         print(f"{name:16s} seed {seed}: GPU median {np.median(e):.1e} p99 {np.percentile(e, 99):.1e} worst {e.max():.1e} | "
               f"reference formulation in fp32: median {np.median(r):.1e} p99 {np.percentile(r, 99):.1e} worst {r.max():.1e}", flush=True)
 
-# [round 5] the rigid contact models in fp32 (the cases of tests/test_gpu_parity.py), same truth: the fp64 oracle on the same state
-from test_gpu_parity import RELAXED_CASES, RIGID_CASES  # noqa: E402
+# [round 5] the rigid contact models in fp32 (the cases of tests/parity_cases.py), same truth: the fp64 oracle on the same state
+from parity_cases import RELAXED_CASES, RIGID_CASES  # noqa: E402
 
 for kind, table, make in (("relaxed", RELAXED_CASES, helpers.relaxed_model), ("rigid", RIGID_CASES, helpers.rigid_model)):
     for key, (name, idx, params) in table.items():
